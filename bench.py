@@ -6,6 +6,7 @@ One *step* = one loss evaluation on a 2-image batch, through the C ABI of libbox
   bxi_boxinst_eval_f32   ONE launch (eval1) at this size: front half (image pool + Lab || logit streaming || table) -> back half (colour
                          predicates + pair-weight sum per image, projection leaders, pairwise term on the box tiles, both loss scalars,
                          FINISHED gradient); other shapes: the same roles as two launches (prep, pair).  `config.kernels_per_step` says which
+                         (with --full: a plain run does not count launches)
 i.e. everything CondInstMaskHead.loss + .backward() do for mask_logits, from the normalised images, boxes and logits
 already resident in HBM to loss_prj, loss_pairwise and d(loss_prj + loss_pairwise)/d(mask_logits); the two upstream
 factors are read from device memory inside the kernels (ones here, as `loss.backward()` seeds them).
@@ -23,6 +24,12 @@ the path is measured beside it, as an extra (`multi_gpu.*_extra`): per evaluatio
 head's `param_conv` parameters (537 065 f32 = 2.15 MB, mmdet/models/detectors/base.py:201-217 + DDP) carrying the two loss scalars in
 its tail, issued asynchronously so that it overlaps the next evaluations.
 Rank 0 prints ONE JSON line on stdout (whatever libraries print there -- RCCL's version banner -- is sent to stderr).
+
+A plain run does only what the headline needs: set up, warm up, time `--steps` evaluations, print the line.  Everything else
+(the C-oracle parity gate and the CPU baseline, the per-rank gates and the all-reduce figures at N > 1, the speed-of-light
+launch behind `roofline`, per-kernel timing, the extras) runs with `--full` only; `--no-*` switch parts of it off.
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's set: the two loss scalars and the gradient w.r.t.
+mask_logits) as .npy files; the inputs are seeded, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -61,7 +68,33 @@ def parse_args(argv=None):
                     help='skip the extra measurements (multi-stream, warm cache, autograd / module API)')
     ap.add_argument('--cpu-seconds', type=float, default=15.0)
     ap.add_argument('--spawn', action='store_true', help='spawn the ranks even for --gpus 1 (exercises the launcher)')
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: parity gates, CPU baseline, speed of light, kernel timing, extras')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.warmup < 0:
+        ap.error('--warmup must be >= 0')
+    return args
+
+
+DUMP_MAX_BYTES = 48 << 20       # the gradient is written whole up to this size, as a fixed seeded sample of its elements above it
+
+
+def dump_outputs(out_dir: str, s: 'EvalSet') -> None:
+    """What a caller of the timed path receives from one evaluation: loss_prj, loss_pairwise, d(loss)/d(mask_logits)."""
+    os.makedirs(out_dir, exist_ok=True)
+    losses = s.losses.cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, 'loss_prj.npy'), losses[0])
+    np.save(os.path.join(out_dir, 'loss_pairwise.npy'), losses[1])
+    grad = s.grad.cpu().numpy().astype(np.float32)
+    if grad.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, 'grad_mask_logits.npy'), grad)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(grad.size, DUMP_MAX_BYTES // 4, replace=False))
+        np.save(os.path.join(out_dir, 'grad_mask_logits_sample.npy'), grad.reshape(-1)[idx])
 
 
 class EvalSet:
@@ -94,6 +127,16 @@ class EvalSet:
                              vp(self.state.data_ptr()), vp(self.grad.data_ptr()))
 
 
+def ensure_built(full: bool) -> None:
+    """The HIP library, compiled only when a source is newer than it: an up-to-date tree is not written to, so the benchmark
+    also runs where the tree is read-only.  --full also needs the C oracle of the parity gates and the CPU baseline: build()."""
+    from boxinstseg_amd import build as hip_build
+    hip_build.build()
+    if full:
+        import __graft_entry__ as entry
+        entry.build()
+
+
 def free_port() -> int:
     import socket
     with socket.socket() as s:
@@ -113,8 +156,7 @@ def main():
         # the launcher of the reference is tools/dist_train.sh:10-20 (torch.distributed.launch, one process per GPU)
         if torch.cuda.device_count() < args.gpus:
             raise SystemExit(f'--gpus {args.gpus} but only {torch.cuda.device_count()} visible device(s)')
-        import __graft_entry__ as entry
-        entry.build()                          # once, before the ranks start
+        ensure_built(args.full)                # once, before the ranks start
         import torch.multiprocessing as mp
         mp.spawn(_spawned, args=(sys.argv[1:], args.gpus, free_port()), nprocs=args.gpus, join=True)
         return
@@ -145,9 +187,8 @@ def worker(args):
             raise SystemExit('--gpus > 1 needs one process per GPU')
     dev = torch.device('cuda', local_rank if dist is not None else 0)
 
-    import __graft_entry__ as entry
     if rank == 0:
-        entry.build()
+        ensure_built(args.full)
     if dist is not None:
         dist.barrier()
     from boxinstseg_amd import _lib, functional as Fh, synthetic
@@ -180,7 +221,7 @@ def worker(args):
     parity = None
     rank_parity = None
     cpu_leg = None
-    if dist is not None and not args.no_cpu_baseline:
+    if dist is not None and args.full and not args.no_cpu_baseline:
         # one process per GPU (any N): EVERY rank checks its own first set against the C oracle before anything is timed (the checker
         # only: the timed CPU baseline stays a rank-0, N == 1 figure), and one rank's mismatch fails the whole run
         rank_parity = parity = parity_gate_only(sets[0])
@@ -189,7 +230,7 @@ def worker(args):
         if float(bad.item()) != 0.0:
             raise SystemExit(f'parity gate failed on some rank (this rank {rank}: {parity}), refusing to time')
     c_oracle_leg = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # the checker first (the C oracle, ~0.1 s): nothing is timed before the HIP result agrees with it.  The TIMED CPU baseline (torch-CPU
         # restatement, tens of seconds on up to 64 threads) runs at the very end: its worker threads otherwise slow every host-bound
         # figure measured after it (module_api: 77 -> 145 us per call behind a 64-thread sample).
@@ -271,17 +312,18 @@ def worker(args):
     prev_stream = torch.cuda.current_stream(dev)
     torch.cuda.set_stream(stream)          # `stream` stays current from here to the end of the timed region
     run(args.warmup)
-    # launches per step, counted: the launch hook is called before and after every kernel launch the library makes
-    calls = []
-    cb_count = _lib.LAUNCH_HOOK(lambda name, phase, st, user: calls.append(name))
-    lib.bxi_dev_set_launch_hook(C.cast(cb_count, C.c_void_p), None)
-    try:
-        enqueue(sets[0], stream.cuda_stream)
-    finally:
-        lib.bxi_dev_set_launch_hook(None, None)
-    torch.cuda.synchronize(dev)
-    launches_per_step = len(calls) // 2
-    launched = sorted({c.decode() for c in calls})
+    launch_count = {}
+    if args.full:
+        # launches per step, counted: the launch hook is called before and after every kernel launch the library makes
+        calls = []
+        cb_count = _lib.LAUNCH_HOOK(lambda name, phase, st, user: calls.append(name))
+        lib.bxi_dev_set_launch_hook(C.cast(cb_count, C.c_void_p), None)
+        try:
+            enqueue(sets[0], stream.cuda_stream)
+        finally:
+            lib.bxi_dev_set_launch_hook(None, None)
+        torch.cuda.synchronize(dev)
+        launch_count = {'launches_per_step': len(calls) // 2, 'kernels_per_step': sorted({c.decode() for c in calls})}
     preroll()
     barrier()
     done = torch.cuda.Event()
@@ -294,12 +336,16 @@ def worker(args):
     torch.cuda.synchronize(dev)
     barrier()
     torch.cuda.set_stream(prev_stream)
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the sets: the buffers of the set the last timed step evaluated
+        dump_outputs(args.dump_outputs, sets[(args.warmup + args.steps - 1) % len(sets)])
     local_elapsed = elapsed
-    allreduce_us = None
+    allreduce_us = with_comm = None
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if dist is not None and args.full:
         # the same all-reduce alone, back to back (what one of them costs when nothing hides it)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
@@ -321,7 +367,7 @@ def worker(args):
     images = 2 * args.steps * world
     value = images / elapsed
     step_us = elapsed / args.steps * 1e6
-    sol = speed_of_light(lib, sets, dev, stream, args.steps, args.warmup) if rank == 0 else None
+    sol = speed_of_light(lib, sets, dev, stream, args.steps, args.warmup) if rank == 0 and args.full else None
 
     result = {
         'metric': 'pairwise+projection loss fwd+bwd images/sec @2x800x1024x32inst',
@@ -331,7 +377,7 @@ def worker(args):
         'config': {'workload': 'BoxInst R-50 FPN loss path, 2x800x1024 synthetic batch, '
                                f'{sets[0].inst.N} instances, 1xMI355X per rank (BASELINE configs[1])',
                    'images_per_step': 2, 'instances': sets[0].inst.N, 'map': [sets[0].inst.h, sets[0].inst.w],
-                   'launch': args.mode, 'launches_per_step': launches_per_step, 'kernels_per_step': launched, 'input_sets': args.sets, 'preroll_s': PREROLL_S,
+                   'launch': args.mode, **launch_count, 'input_sets': args.sets, 'preroll_s': PREROLL_S,
                    'parallelism': f'replicas x{world} (no exchange step inside the path)'},
     }
     if dist is not None:
@@ -346,16 +392,18 @@ def worker(args):
         result['multi_gpu'] = {
             'world_size': dist.get_world_size(), 'backend': 'nccl (RCCL)', 'ranks': ranks,
             'distinct_devices': len({(r['pci_bus_id'], r['uuid']) for r in ranks}),
-            'per_rank_images_per_s': 2 * args.steps / local_elapsed,
-            'per_rank_images_per_s_with_bucket_allreduce_extra': 2 * args.steps / with_comm,
-            'allreduce_per_evaluation_extra': f'{(PARAM_CONV_FLOATS + 2) * 4} B (param_conv-sized gradient bucket + the 2 loss scalars), '
-                                              'async, overlapping the following evaluations; NOT part of `value`: the path has no '
-                                              'exchange step, this is what DDP does around it',
-            'allreduce_alone_us': allreduce_us}
+            'per_rank_images_per_s': 2 * args.steps / local_elapsed}
+        if with_comm is not None:
+            result['multi_gpu'].update({
+                'per_rank_images_per_s_with_bucket_allreduce_extra': 2 * args.steps / with_comm,
+                'allreduce_per_evaluation_extra': f'{(PARAM_CONV_FLOATS + 2) * 4} B (param_conv-sized gradient bucket + the 2 loss scalars), '
+                                                  'async, overlapping the following evaluations; NOT part of `value`: the path has no '
+                                                  'exchange step, this is what DDP does around it',
+                'allreduce_alone_us': allreduce_us})
     if parity is not None:
         result['parity'] = parity
 
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras
     # the extras are not `value`: each runs its own count of steps (the driver's 20-step invocation is too short a sample for them)
     n_extra = max(args.steps, 300)
     # ---- extra (not `value`): independent evaluations pipelined over several HIP streams ------------------------
@@ -423,7 +471,7 @@ def worker(args):
         result['module_api'] = module_api(sets, dev, 300)
 
     # ---- per-kernel durations with HIP events on the launching stream (rank 0, N == 1) ------------
-    if rank == 0 and world == 1 and not args.no_kernel_timing:
+    if rank == 0 and world == 1 and args.full and not args.no_kernel_timing:
         result.update(kernel_timing(lib, _lib, sets, stream, enqueue, min(max(args.steps, 50), 200), step_us, status[1]))
     if sol is not None:
         # the floor of THIS launch shape on this part, measured in the same run on the same cold sets: the evaluation's bytes moved by

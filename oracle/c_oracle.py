@@ -22,7 +22,15 @@ def build(force: bool = False) -> str:
     # checked against a stale library; under a file lock, so that concurrent test processes do not rebuild it at once
     import fcntl
     os.makedirs(os.path.join(_HERE, '_build'), exist_ok=True)
-    with open(os.path.join(_HERE, '_build', '.lock'), 'w') as lk:
+    try:
+        lk = open(os.path.join(_HERE, '_build', '.lock'), 'w')
+    except OSError:
+        # a tree this process may not write to (built by another user): usable as built, if `make -q` finds it up to date
+        if not force and os.path.exists(_SO) and subprocess.run(['make', '-q', '-C', _HERE], stdout=subprocess.DEVNULL,
+                                                                stderr=subprocess.DEVNULL).returncode == 0:
+            return _SO
+        raise
+    with lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         subprocess.run(['make', '-C', _HERE] + (['-B'] if force else []), check=True, stdout=subprocess.DEVNULL)
     return _SO

@@ -86,7 +86,7 @@ def test_bench_spawns_its_own_ranks(dev):
     n = min(2, torch.cuda.device_count())
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--spawn', '--steps', '40', '--warmup', '10',
-           '--no-cpu-baseline', '--no-extras', '--no-kernel-timing']
+           '--full', '--no-cpu-baseline', '--no-extras', '--no-kernel-timing']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=800, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')][-1]

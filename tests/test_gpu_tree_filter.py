@@ -152,10 +152,31 @@ def test_refine_vs_reference_kernels_fixture(built, dev, case):
     assert np.abs(gw - want_gw).max() <= 2e-5 * max(1.0, np.abs(want_gw).max())
 
 
-@pytest.mark.skipif(not tfo.ref_kernels_available(), reason='oracle/_ref/libtreekernels_ref.so not built (make -C oracle ref)')
+def _ref_refine_live(name, tree, x, g, w_vertex, V):
+    """(out, feature gradient, per-vertex edge-weight gradient) of the reference's own bfs.cu / refine.cu kernels on `tree`,
+    as tests/golden/ref_kernels_live.npz holds them (tests/golden/make_ref_live.py, computed on the same tree).  Where
+    oracle/_ref is built (make -C oracle ref, from the reference tree) the kernels also run on this host's CPU and must
+    reproduce the fixture (to rounding: the emulation's atomics arrive in no fixed order)."""
+    import hashlib
+    gold = np.load(os.path.join(GOLD, 'ref_kernels_live.npz'))
+    e = np.sort(np.asarray(tree, np.int64).reshape(-1, 2), axis=1)
+    e = np.ascontiguousarray(e[np.lexsort((e[:, 1], e[:, 0]))])
+    assert hashlib.sha256(e.tobytes()).hexdigest() == str(gold[f'{name}_tree_sha256']), 'not the tree of the fixture'
+    want = gold[f'{name}_out'], gold[f'{name}_gf'], gold[f'{name}_gw']
+    if tfo.ref_kernels_available():
+        r_si, r_sp, r_sc = tfo.ref_bfs(tree, V)
+        fwd = tfo.ref_refine_forward(x, w_vertex[r_si], r_si, r_sp, r_sc)
+        r_gf, r_gw = tfo.ref_refine_backward(g, w_vertex[r_si], r_si, r_sp, r_sc, fwd)
+        want_gw = np.zeros(V, np.float32); want_gw[r_si] = r_gw
+        live = fwd['out'], r_gf, want_gw
+        for got, fix in zip(live, want):
+            assert got.shape == fix.shape and np.abs(got - fix).max() <= 1e-6 * max(1.0, np.abs(fix).max()), 'fixture is stale'
+        return live
+    return want
+
+
 def test_refine_vs_reference_kernels_live_96x96(built, dev):
-    """the same comparison at Box2Mask's size, the reference kernels run on this host's CPU (the .so travels with the
-    snapshot; built from the reference tree in the build container only)"""
+    """the same comparison at Box2Mask's size, against the reference kernels (_ref_refine_live)"""
     from boxinstseg_amd import mst
     rng = np.random.default_rng(77)
     H = W = 96
@@ -163,16 +184,13 @@ def test_refine_vs_reference_kernels_live_96x96(built, dev):
     idx = tfo.grid_edges(H, W)
     fm = rng.standard_normal((3, H, W)).astype(np.float32)
     tree = mst(torch.from_numpy(idx)[None].to(dev), torch.from_numpy(tfo.grid_weights(fm))[None].to(dev), V)[0].cpu().numpy()
-    r_si, r_sp, r_sc = tfo.ref_bfs(tree, V)
     C = 2
     x = rng.standard_normal((C, V)).astype(np.float32)
     g = rng.standard_normal((C, V)).astype(np.float32)
     w_vertex = np.exp(-rng.random(V) * 0.8).astype(np.float32)
-    fwd = tfo.ref_refine_forward(x, w_vertex[r_si], r_si, r_sp, r_sc)
-    r_gf, r_gw = tfo.ref_refine_backward(g, w_vertex[r_si], r_si, r_sp, r_sc, fwd)
-    want_gw = np.zeros(V, np.float32); want_gw[r_si] = r_gw
+    fwd_out, r_gf, want_gw = _ref_refine_live('tf96', tree, x, g, w_vertex, V)
     out, gf, gw = _hip_refine_per_vertex(dev, tree, x, w_vertex, g)
-    assert np.abs(out - fwd['out']).max() <= 1e-5 * max(1.0, np.abs(fwd['out']).max())
+    assert np.abs(out - fwd_out).max() <= 1e-5 * max(1.0, np.abs(fwd_out).max())
     assert np.abs(gf - r_gf).max() <= 1e-5 * max(1.0, np.abs(r_gf).max())
     assert np.abs(gw - want_gw).max() <= 1e-4 * max(1.0, np.abs(want_gw).max())
 
@@ -514,10 +532,9 @@ def test_large_refine_tree_shapes(built, dev, shape, large_form):
     assert np.abs(xd.grad[0].cpu().numpy() - gf).max() <= 2e-5 * max(np.abs(gf).max(), 1.0)
 
 
-@pytest.mark.skipif(not tfo.ref_kernels_available(), reason='oracle/_ref/libtreekernels_ref.so not built (make -C oracle ref)')
 def test_large_refine_vs_reference_kernels_live_200x304(built, dev):
-    """BoxLevelSet's size against the reference's OWN bfs.cu / refine.cu kernels run on this host's CPU
-    (oracle/_ref/libtreekernels_ref.so travels with the snapshot): the BFS orders differ, the results per vertex must not."""
+    """BoxLevelSet's size against the reference's OWN bfs.cu / refine.cu kernels (_ref_refine_live): the BFS orders differ,
+    the results per vertex must not."""
     from boxinstseg_amd import mst
     rng = np.random.default_rng(78)
     H, W = 200, 304
@@ -525,16 +542,13 @@ def test_large_refine_vs_reference_kernels_live_200x304(built, dev):
     idx = tfo.grid_edges(H, W)
     fm = rng.standard_normal((3, H, W)).astype(np.float32)
     tree = mst(torch.from_numpy(idx)[None].to(dev), torch.from_numpy(tfo.grid_weights(fm))[None].to(dev), V)[0].cpu().numpy()
-    r_si, r_sp, r_sc = tfo.ref_bfs(tree, V)
     C = 1
     x = rng.standard_normal((C, V)).astype(np.float32)
     g = rng.standard_normal((C, V)).astype(np.float32)
     w_vertex = np.exp(-rng.random(V) * 0.8).astype(np.float32)
-    fwd = tfo.ref_refine_forward(x, w_vertex[r_si], r_si, r_sp, r_sc)
-    r_gf, r_gw = tfo.ref_refine_backward(g, w_vertex[r_si], r_si, r_sp, r_sc, fwd)
-    want_gw = np.zeros(V, np.float32); want_gw[r_si] = r_gw
+    fwd_out, r_gf, want_gw = _ref_refine_live('tf200x304', tree, x, g, w_vertex, V)
     out, gf, gw = _hip_refine_per_vertex(dev, tree, x, w_vertex, g)
-    assert np.abs(out - fwd['out']).max() <= 1e-5 * max(1.0, np.abs(fwd['out']).max())
+    assert np.abs(out - fwd_out).max() <= 1e-5 * max(1.0, np.abs(fwd_out).max())
     assert np.abs(gf - r_gf).max() <= 1e-5 * max(1.0, np.abs(r_gf).max())
     assert np.abs(gw - want_gw).max() <= 1e-4 * max(1.0, np.abs(want_gw).max())
 

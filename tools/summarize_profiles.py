@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Turn the rocprofv3 outputs merged into gpurun_out/ into the tracked summaries under profiles/.
+"""Turn the rocprofv3 outputs merged into profile_out/ into the tracked summaries under profiles/.
 
     python tools/summarize_profiles.py r02        (after `gpurun -- tools/gpu_profiles.sh r02`)
 
-reads  gpurun_out/prof_eager/<round>_kernel_stats.csv                    (rocprofv3 --kernel-trace --stats)
-       gpurun_out/pmc_FETCH_SIZE|pmc_WRITE_SIZE/<round>_counter_collection.csv  (one --pmc pass per counter)
-       gpurun_out/prof_<row>/<round>_kernel_stats.csv, gpurun_out/<row>_bench.json, gpurun_out/block_trace.txt, bench_default.json
+reads  profile_out/prof_eager/<round>_kernel_stats.csv                    (rocprofv3 --kernel-trace --stats)
+       profile_out/pmc_FETCH_SIZE|pmc_WRITE_SIZE/<round>_counter_collection.csv  (one --pmc pass per counter)
+       profile_out/prof_<row>/<round>_kernel_stats.csv, profile_out/<row>_bench.json, profile_out/block_trace.txt, bench_default.json
 writes profiles/<round>_kernel_stats_eager.csv, profiles/<round>_hbm_traffic.json, profiles/<round>_summary.md
 FETCH_SIZE is doubled for the streaming kernel, as MI355X_MICROARCH.md prescribes for 16 B/lane coalesced
 reads on gfx950 (the counter tallies 128-B requests at 64 B); WRITE_SIZE is used as reported (KB).
@@ -18,7 +18,7 @@ import shutil
 import sys
 
 rnd = sys.argv[1] if len(sys.argv) > 1 else 'r02'
-G, P = 'gpurun_out', 'profiles'
+G, P = os.environ.get('OUT', 'profile_out'), 'profiles'
 os.makedirs(P, exist_ok=True)
 shutil.copy(f'{G}/prof_eager/{rnd}_kernel_stats.csv', f'{P}/{rnd}_kernel_stats_eager.csv')
 for row in ('pairwise_op', 'dynamic_head', 'head_fused', 'discobox', 'levelset', 'tree_filter', 'two_launch', 'n64', 'n128', 'n128_fold', 'n128_long',
@@ -53,12 +53,12 @@ for k, t in traffic.items():
     fetch = t.get('FETCH_SIZE_KB', 0.0) * 1024 * 2      # gfx950: x2 for wide coalesced reads
     write = t.get('WRITE_SIZE_KB', 0.0) * 1024
     out[k] = dict(fetch_bytes_corrected=fetch, write_bytes=write, hbm_bytes=fetch + write, raw=t)
-json.dump(dict(round=rnd, command='python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-kernel-timing --no-extras', kernels=out,
+json.dump(dict(round=rnd, command='python bench.py --steps 100 --warmup 20 --full --no-cpu-baseline --no-kernel-timing --no-extras', kernels=out,
                note='rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes; FETCH_SIZE x2 (gfx950 correction, '
                     'MI355X_MICROARCH.md section HBM); per launch, mean over the timed launches'),
           open(f'{P}/{rnd}_hbm_traffic.json', 'w'), indent=1)
 with open(f'{P}/{rnd}_summary.md', 'w') as f:
-    f.write(f'# rocprofv3 summary, round {rnd[1:]} (MI355X, `rocprofv3 --kernel-trace --stats -- python bench.py --steps 400 --warmup 50 --no-cpu-baseline --no-kernel-timing --no-extras`)\n\n')
+    f.write(f'# rocprofv3 summary, round {rnd[1:]} (MI355X, `rocprofv3 --kernel-trace --stats -- python bench.py --steps 400 --warmup 50 --full --no-cpu-baseline --no-kernel-timing --no-extras`)\n\n')
     f.write('| kernel | calls | avg us | min us | max us | HBM read (PMC, corrected) MB | HBM write (PMC) MB |\n|---|---:|---:|---:|---:|---:|---:|\n')
     for k, s in sorted(stats.items(), key=lambda kv: -kv[1]['avg_us']):
         t = out.get(k, {})
@@ -67,7 +67,7 @@ with open(f'{P}/{rnd}_summary.md', 'w') as f:
 print(open(f'{P}/{rnd}_summary.md').read())
 
 # ---- the "next" rows: one table per tracked rocprofv3 kernel-stats file under profiles/ ------------------
-BENCH = 'bench.py --steps 400 --warmup 50 --no-cpu-baseline --no-kernel-timing --no-extras'
+BENCH = 'bench.py --steps 400 --warmup 50 --full --no-cpu-baseline --no-kernel-timing --no-extras'
 EXTRA = [('two_launch', 'the same evaluation in its two-launch form (`--flags 2` = BXI_EVAL_TWO_LAUNCHES)', BENCH + ' --flags 2'),
          ('n64', '64 instances (2 per box), default form', BENCH + ' --inst-per-box 2 --sets 6'),
          ('n128', '128 instances (4 per box: what configs/boxinst/boxinst_r50_fpn_1x_coco.py:65,125 trains at), default form', BENCH + ' --inst-per-box 4 --sets 6'),
