@@ -29,9 +29,12 @@
 //                   the tile's share of sum W pw goes to an integer accumulator by an atomic without return.  Its two waits:
 //                   its own predicate bytes (bit 7 = evaluated) before the pair loop, the published sum W (the global
 //                   normaliser) after it; both are produced by workgroups that precede it in the grid and never wait
-//                   for a tile.
+//                   for a tile.  In the single-launch forms the wave ARRIVES (its share) as soon as the pair loop of its last tile
+//                   is done, ahead of that tile's wait for sum W and its adds: the finisher reads nothing else of it.  A wait that runs out after the
+//                   arrival is loud by itself (NaN gradient elements, fault and status words, NaN losses).
 //     finisher      the last workgroup: polls the accumulators (every tile wave arrives exactly once, with or without tiles), writes the two
-//                   loss values and, as its last act, advances the workspace's epoch.
+//                   loss values and, as its last act, advances the workspace's epoch -- while the last tile waves may still be
+//                   waiting for sum W and adding (single-launch forms): the launch ends at the later of the two.
 // What one workgroup hands to another inside a launch carries the evaluation's TAG = epoch + 1; the epoch is word 0 of the workspace,
 // read on the device by every kernel of an evaluation (with_tag) -- nothing about it is a kernel argument, so a captured launch replayed
 // from a hipGraph is as correct as an eager one; the warm-up factor likewise (resolve_warmup).  The workspace is zeroed once and keeps ONE
@@ -1107,10 +1110,39 @@ __device__ __forceinline__ bool pred_words(const Ws& ws, const Tile& t, int h, i
     return ok;        // false: the caller's arrival says so, and the finisher turns both losses into NaN
 }
 
+// A tile wave's ONE arrival, with or without tiles: its share of sum W pw (+ 1.0: keeps the packed field non-negative -- S may exceed 1 by
+// a rounding) and whether one of its bounded waits ran out, as one atomic without return on one of the N x 8 arrival words (each in its
+// own 128 bytes).  The finisher counts WAVES, so its last act -- advancing the workspace's epoch -- comes after every tile wave of
+// the launch has read the epoch (an idle wave that started late could otherwise draw the NEXT evaluation's tag and wait for nobody).
+// WHICH word: one of an instance whose table entry this wave has SEEN tagged -- the table wave of instances 64 k .. 64 k + 63 zeroes their arrival
+// words and drains before it writes their entries, and a tile wave checks entries 0 .. 63 and N only (tile_role).  Rounds 3-5 spread the arrivals
+// over all N x 8 words: in the single-launch forms a tile wave could then arrive on a word of instances 64 .. N - 1 that the SECOND table wave --
+// draining its written-through zeroes under the logit stream's traffic -- had not zeroed yet; the zero wiped the arrival, the finisher never saw its
+// count, ran out (status 2, NaN losses for that evaluation) after kSpinLimit polls = 4.1 s.  Seen five times in 4800 evaluations with the 8-row
+// kernels at four workgroups per CU and 128 instances, where the tile workgroups start just as the stream workgroups' traffic lets the table's
+// drains complete (profiles/NOTES.md R5-7, R6-3: the stall's length follows kSpinLimit, the wait that runs out is the finisher's).
+// A wave whose bounded wait ran out (or that saw a fault word) says so on the evaluation's fault word BEFORE it arrives -- a returning atomic, waited
+// for -- so that the round in which the finisher sees the last arrival sees the fault too.  (Rounds 3-5 added a flag bit to the arrival itself: with
+// six arrivals per word four faults carry into the arrival count, the finisher never sees the count it waits for and the -- already loud -- error path
+// takes kSpinLimit polls: 4.5 s for an evaluation whose targets are somebody else's.)
+// WHEN: as soon as the share is complete -- behind the pair math of the wave's LAST tile, ahead of that tile's wait for sum W / the band flags
+// and its adds (math_tile) --; a wave without tiles, or whose earlier wait ran out, after its tile loop; in the two-launch form and in the wrap
+// evaluation (tag kMaxTag) after its adds -- there so that the finisher's zeroing of the workspace comes after every read of it (tile_role).
+__device__ __forceinline__ void tile_wave_arrives(const Ws& ws, int N, int wid, long long fx_sum, bool bad) {
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) {
+            const unsigned int seen = __hip_atomic_fetch_or(ws.fault, kFaultCounts, BXI_RLX, BXI_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::"v"(seen) : "memory");
+        }
+        __hip_atomic_fetch_add(ws.acc2 + (size_t)(wid % ((N < 64 ? N : 64) * kAcc2Split)) * kAcc2Stride,
+                               (1ull << 52) + (unsigned long long)(fx_sum + (1ll << 24)), BXI_RLX, BXI_AGENT);
+    }
+}
+
 template <int D, int R, bool ONE>
 __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const Tile& t, float upw_warm, float n2max, int zero_bit, int n_items,
                                           int spin_limit, float& scale, bool& have_scale, float* __restrict__ g_logits, float* gbuf /* LDS [R + 1][64] of this wave */,
-                                          int tix, long long& fx_sum, bool& bad_out) {
+                                          int tix, long long& fx_sum, bool& bad_out, bool arrive, const LossState& st, float* __restrict__ losses) {
     constexpr int RD = TG<D, R>::RD;
     const int lane = threadIdx.x & 63;
     const int h = a.h, w = a.w, n = t.n;
@@ -1323,6 +1355,10 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
     BXI_TW(1, tix, 5);
     num = wave_total_f32(num);
     fx_sum += (long long)(num * kNumScale);                                    // this tile's share of sum W pw, fixed point: integer adds commute
+    // `arrive` (the wave's last tile, outside the wrap evaluation -- tile_role): the wave's share of sum W pw is complete, and it is all the
+    // finisher needs of it.  So the wave arrives HERE, ahead of its wait for sum W / the band flags and of its adds: the finisher no longer
+    // waits for three hops whose results it never reads, and the launch ends at the later of the last tile wave's adds and the finisher's store.
+    if (arrive) tile_wave_arrives(ws, a.N, tix, fx_sum, bad);
     // single-launch form: the rows this tile adds onto were zero-filled by stream workgroups of THIS launch; their band flags are
     // asked for in the same round as sum W
     bool bands_ok = !ONE || !g_logits;
@@ -1357,7 +1393,27 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
         have_scale = true;
     }
     BXI_TW(1, tix, 4);
-    if (g_logits) {
+    if (arrive && bad) {      // wave-uniform; never expected
+        // A wave that has arrived cannot tell the finisher any more: it is loud by itself -- NaN in its tile's gradient elements, the fault word,
+        // the status word and NaN losses.  Ordering: a wait that runs out after the arrival has polled for kSpinLimit rounds (seconds), while the
+        // finisher, which needs nothing of this wave beyond its arrival, has stored the losses and the status microseconds after the last arrival:
+        // these stores come long after the finisher's, and rescale_kernel (a later launch) sees the status.  (A fault word or a sum W fault bit seen
+        // here the finisher sees as well: it publishes NaN by itself.)  The wrap evaluation keeps the old order (tile_role): nothing of this wave
+        // touches the workspace after its arrival there.
+        if (g_logits) {
+            float* G = g_logits + (int64_t)n * P;
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const int r = t.tile_r0 + j;
+                if (col_owned && r < h) G[(int64_t)r * w + c] = __int_as_float(0x7fc00000);
+            }
+        }
+        if (lane == 0) {
+            atomicOr(ws.fault, kFaultCounts);
+            if (st.status) atomicOr(st.status, (int)kFaultCounts);
+            losses[0] = __int_as_float(0x7fc00000); losses[1] = losses[0];
+        }
+    } else if (g_logits) {
         char* G = reinterpret_cast<char*>(g_logits + (int64_t)n * P);      // scalar base + 32-bit byte offset
 #pragma unroll
         for (int j = 0; j < R; ++j) {
@@ -1367,32 +1423,6 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
     }
     BXI_TW(1, tix, 6);
     bad_out |= bad;
-}
-
-// A tile wave's ONE arrival, with or without tiles: its share of sum W pw (+ 1.0: keeps the packed field non-negative -- S may exceed 1 by
-// a rounding) and whether one of its bounded waits ran out, as one atomic without return on one of the N x 8 arrival words (each in its
-// own 128 bytes).  The finisher counts WAVES, so its last act -- advancing the workspace's epoch -- comes after every tile wave of
-// the launch has read the epoch (an idle wave that started late could otherwise draw the NEXT evaluation's tag and wait for nobody).
-// WHICH word: one of an instance whose table entry this wave has SEEN tagged -- the table wave of instances 64 k .. 64 k + 63 zeroes their arrival
-// words and drains before it writes their entries, and a tile wave checks entries 0 .. 63 and N only (tile_role).  Rounds 3-5 spread the arrivals
-// over all N x 8 words: in the single-launch forms a tile wave could then arrive on a word of instances 64 .. N - 1 that the SECOND table wave --
-// draining its written-through zeroes under the logit stream's traffic -- had not zeroed yet; the zero wiped the arrival, the finisher never saw its
-// count, ran out (status 2, NaN losses for that evaluation) after kSpinLimit polls = 4.1 s.  Seen five times in 4800 evaluations with the 8-row
-// kernels at four workgroups per CU and 128 instances, where the tile workgroups start just as the stream workgroups' traffic lets the table's
-// drains complete (profiles/NOTES.md R5-7, R6-3: the stall's length follows kSpinLimit, the wait that runs out is the finisher's).
-// A wave whose bounded wait ran out (or that saw a fault word) says so on the evaluation's fault word BEFORE it arrives -- a returning atomic, waited
-// for -- so that the round in which the finisher sees the last arrival sees the fault too.  (Rounds 3-5 added a flag bit to the arrival itself: with
-// six arrivals per word four faults carry into the arrival count, the finisher never sees the count it waits for and the -- already loud -- error path
-// takes kSpinLimit polls: 4.5 s for an evaluation whose targets are somebody else's.)
-__device__ __forceinline__ void tile_wave_arrives(const Ws& ws, int N, int wid, long long fx_sum, bool bad) {
-    if ((threadIdx.x & 63) == 0) {
-        if (bad) {
-            const unsigned int seen = __hip_atomic_fetch_or(ws.fault, kFaultCounts, BXI_RLX, BXI_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::"v"(seen) : "memory");
-        }
-        __hip_atomic_fetch_add(ws.acc2 + (size_t)(wid % ((N < 64 ? N : 64) * kAcc2Split)) * kAcc2Stride,
-                               (1ull << 52) + (unsigned long long)(fx_sum + (1ll << 24)), BXI_RLX, BXI_AGENT);
-    }
 }
 
 __device__ __forceinline__ void block_sum4(float (&v)[4], float* red /*[16]*/) {
@@ -1726,6 +1756,9 @@ __device__ __forceinline__ void finisher_role(const InstArgs& a, const Ws& ws, c
         if (++spins > spin_limit) { ok = false; break; }           // workgroup-uniform: the same count in every thread
     }
     BXI_WL(10, spins);
+    // ... and once more past the round that saw the last arrival: the read in that round may have been served before a late wave's fetch_or,
+    // which that wave waits for before its arrival (tile_wave_arrives); this read comes after the arrival was seen.  (In flight under the sum below.)
+    if (threadIdx.x == 0) fault_seen |= __hip_atomic_load(ws.fault, BXI_RLX, BXI_AGENT);
     const double wsum = wave_total_f64((double)mine);                // exact; fixed order: run-to-run identical
     if (lane == 0) fin_d[wave] = wsum;
     __syncthreads();
@@ -1748,7 +1781,8 @@ __device__ __forceinline__ void finisher_role(const InstArgs& a, const Ws& ws, c
         // The tag counter is about to wrap: records of 2^28 evaluations ago would pass for fresh ones (table entries and arrival words of
         // instances beyond the current count keep their tags until an evaluation that large comes again).  So this evaluation ends by
         // returning the workspace to its initial state -- all zero, epoch 0 -- as bxi_boxinst_eval_workspace_init does: every other wave
-        // has arrived, and in this evaluation every wave drains its stores before it arrives (pred_role; the others always do).
+        // has arrived, and in this evaluation every wave drains its stores before it arrives (pred_role; the others always do) and arrives
+        // behind its last read of the workspace (tile waves: after their adds in this evaluation only -- tile_role).
         // Once per 2^28 - 1 evaluations, ~3 MB by one wave.  (Targets an earlier bxi_boxinst_targets_f32 left in the workspace go too:
         // an evaluation that counts on them finds key 0 and says so, loud.)
         uint4* z = reinterpret_cast<uint4*>(ws.epoch);
@@ -1761,7 +1795,7 @@ __device__ __forceinline__ void finisher_role(const InstArgs& a, const Ws& ws, c
 // tile workgroup: 4 independent waves striding through the tile list (its length is device data)
 template <int D, int R, bool ONE>
 __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& vc, const Ws& ws, float upw_warm, float n2max, int zero_bit, int n_items, int spin_limit,
-                                          float* __restrict__ g_logits, unsigned char* smem, int tblk, int n_tb) {
+                                          float* __restrict__ g_logits, unsigned char* smem, int tblk, int n_tb, const LossState& st, float* __restrict__ losses) {
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     const int N = a.N;
     const int wid = tblk * kWaves + wave, nwaves = n_tb * kWaves;
@@ -1806,14 +1840,22 @@ __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& v
     // (tiles are dealt wave by wave: the first workgroups' four waves each take one, the last quarter of the workgroups at 128 instances none.
     // Dealt workgroup by workgroup -- three per workgroup, nine per CU instead of twelve or eight -- the launch is SLOWER: 38.4 vs 37.2 us at 128
     // instances, 32.1 vs 31.1 at 96, targets ready 30.3 vs 28.7: the early workgroups' waves start their chains first.  profiles/NOTES.md R6-5)
+    // The wave's last tile arrives from inside math_tile, as soon as its share is known (tile_wave_arrives).  Not in the wrap evaluation: there
+    // the finisher zeroes the workspace once every tile wave has arrived, so every tile wave arrives behind its last read of the workspace.
+    // Single-launch forms only: in the second launch of the two-launch form (128 instances, 8-row tiles) the early arrival measured 0.3-0.4 us
+    // SLOWER (30.0 -> 30.4 us; profiles/NOTES.md R6-28), and without it pair_kernel is the code it was.
+    const bool may_arrive_early = ONE && ws.ep != kMaxTag;
+    bool arrived = false;
     for (int ti = wid; ti < total && !bad; ti += nwaves) {
         if (BXI_AB(256) && (ti & 7) == 7) continue;              // (ablation only: an eighth of the tiles gone -- what fewer tile waves would be worth)
         Tile t;
         if (!locate_tile<D, R, ONE>(ws, vc, N, e0, e1, ti, a.h, a.w, spin_limit, t)) { bad = true; break; }
         BXI_TW(1, wid, 1);
-        math_tile<D, R, ONE>(a, ws, t, upw_warm, n2max, zero_bit, n_items, spin_limit, scale, have_scale, g_logits, gbuf, wid, fx_sum, bad);
+        const bool last = may_arrive_early && ti + nwaves >= total;
+        math_tile<D, R, ONE>(a, ws, t, upw_warm, n2max, zero_bit, n_items, spin_limit, scale, have_scale, g_logits, gbuf, wid, fx_sum, bad, last, st, losses);
+        arrived = last;
     }
-    tile_wave_arrives(ws, N, wid, fx_sum, bad);
+    if (!arrived) tile_wave_arrives(ws, N, wid, fx_sum, bad);
     BXI_TW(1, wid, 7);
 }
 
@@ -1895,7 +1937,7 @@ __global__ __launch_bounds__(256, (R == 4 ? (D <= 2 ? 4 : 3) : (D <= 2 ? 3 : 2))
         BXI_TW(3, 1 + blk - lead0, 0);
         leader_block<false>(a, D, ws, st, blk - lead0, upp, g_logits, smem, red, spin_limit);
     } else {
-        tile_role<D, R, false>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, zero_bit, n_items, spin_limit, g_logits, smem, blk - tile0, n_tb);
+        tile_role<D, R, false>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, zero_bit, n_items, spin_limit, g_logits, smem, blk - tile0, n_tb, st, losses);
     }
 }
 
@@ -2008,7 +2050,7 @@ __global__ __launch_bounds__(256, (R == 4 ? kOneOcc : BXI_LONG_OCC)) void eval1_
     }
     if (role == 4) {          // ONE call site for the stream workgroups that stay on and for the tile workgroups proper
         const int shift = merge ? n_stream : 0;
-        tile_role<D, R, true>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, 0, n_items, spin_limit, g_logits, smem, idx + shift, n_tb + shift);
+        tile_role<D, R, true>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, 0, n_items, spin_limit, g_logits, smem, idx + shift, n_tb + shift, st, losses);
         return;
     }
     finisher_role<true>(a, ws, st, upp, upw, resolve_warmup(warmup, st.iter), 0, n_items, spin_limit, R, (n_tb + (merge ? n_stream : 0)) * kWaves, losses);
