@@ -29,12 +29,6 @@ FLAGS = [f'--offload-arch={ARCH}', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-
          '-mllvm', '-amdgpu-kernarg-preload-count=16']
 
 
-def command(extra: List[str] | None = None, out: str | None = None) -> List[str]:
-    """The one-command form (every source in one hipcc call): what a maintainer would type; build() below compiles the
-    same sources with the same flags, one object per source in parallel, and links them."""
-    return [hipcc(), *FLAGS, '-shared', *(extra or []), '-o', out or LIB_PATH, *[os.path.join(CSRC, s) for s in SOURCES]]
-
-
 def is_stale() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
@@ -56,14 +50,15 @@ def _compile_and_link(out: str, extra: List[str], verbose: bool) -> None:
             return obj
         with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as pool:
             objs = list(pool.map(one, SOURCES))
-        link = [hipcc(), f'--offload-arch={ARCH}', '-shared', '-fPIC', '-o', out, *objs]
+        link = [hipcc(), f'--offload-arch={ARCH}', '-shared', '-fPIC', *extra, '-o', out, *objs]
         if verbose:
             print(' '.join(link))
         subprocess.run(link, check=True)
 
 
 def build(force: bool = False, verbose: bool = False, extra: List[str] | None = None) -> str:
-    """Compile every HIP source into boxinstseg_amd/lib/libboxinst_hip.so; returns its path."""
+    """Compile every HIP source into boxinstseg_amd/lib/libboxinst_hip.so; returns its path.  `extra` goes to every compile
+    and to the link."""
     if force or is_stale():
         import fcntl
         os.makedirs(LIB_DIR, exist_ok=True)

@@ -790,21 +790,14 @@ int bxi_dynamic_mask_backward_f32(const float* feat, int B, int C, int H, int W,
     const int cin = C + (a.rel ? 2 : 0);
     const size_t lds = sizeof(float) * ((size_t)(1 + 4 * bxi::kDC + cin + 2) * bxi::kRowPad);
     // Workgroups per (image, tile): each walks every slots-th instance of its image.
-#ifdef BXI_DEV
-    static const int form = getenv("BXI_DYN_BWD_FORM") ? atoi(getenv("BXI_DYN_BWD_FORM")) : 2;      // A/B of the two forms (developer build only)
-    static const int env_slots = getenv("BXI_DYN_BWD_SLOTS") ? atoi(getenv("BXI_DYN_BWD_SLOTS")) : 0;
-#else
-    constexpr int form = 2, env_slots = 0;
-#endif
     int slots;
-    if (form == 2 && (factor == 1 || factor == 2)) {
+    if (factor == 1 || factor == 2) {
         // dyn_bwd2_kernel, four workgroups per CU (1024 slots on 256 CUs): as many slots per (image, tile) as keep the launch resident at
         // once -- 2 x 52 x 8 = 832 workgroups at 2 x 100 x 128 --, all of them when there are many instances.  Measured against dyn_bwd_kernel
         // (rocprofv3, same box, 2 x 16 x 100 x 128 -> 200 x 256): 32 instances 28.2-28.8 -> 27.2-27.8 us (the reduction over 8 instead of 4
         // feature partials: 5.1 -> 5.6 us), 128 instances 78.6-79.4 -> 70.0-70.8 us; 4 / 6 / 7 slots at 32 instances: 31.3 / 29.8 / 29.9 us.
         const int cap = 4 * bxi::device_cus() / (B * T);
         slots = N > 16 * B || cap >= bxi::kSlots ? bxi::kSlots : (cap < 1 ? 1 : cap);
-        if (env_slots > 0) slots = env_slots;
         const size_t lds2 = sizeof(float) * ((size_t)(cin + 1 + 16 + 2) * bxi::kRowPad);
         const unsigned grid2 = (unsigned)(B * T * slots);
 #define BXI_DYN2(KC, KR, KF) BXI_LAUNCH("dyn_bwd", s, (bxi::dyn_bwd2_kernel<KC, KR, KF>), dim3(grid2), dim3(256), lds2, s, a, params, params, g_logits, feat_part, param_part, slots)
@@ -818,15 +811,10 @@ int bxi_dynamic_mask_backward_f32(const float* feat, int B, int C, int H, int W,
         // dyn_bwd_kernel (factor 4 and the run-time factor: their (2f-1)^2 tap windows do not fit dyn_bwd2_kernel's registers), two workgroups per
         // CU.  Few instances per image: 4 slots, so that the launch is resident at once (2 x 52 x 4 = 416 workgroups on 512 slots); many: 8.
         slots = N <= 16 * B ? 4 : bxi::kSlots;
-        if (env_slots > 0) slots = env_slots;
         const unsigned grid = (unsigned)(B * T * slots);
 #define BXI_DYN1(KC, KR, KF) BXI_LAUNCH("dyn_bwd", s, (bxi::dyn_bwd_kernel<KC, KR, KF>), dim3(grid), dim3(256), lds, s, a, params, params, g_logits, feat_part, param_part, slots)
 #define BXI_DYN1_F(KF) do { if (C == 16 && a.rel) BXI_DYN1(16, true, KF); else if (C == 16) BXI_DYN1(16, false, KF); else if (a.rel) BXI_DYN1(8, true, KF); else BXI_DYN1(8, false, KF); } while (0)
         if (factor == 4) BXI_DYN1_F(4);
-#ifdef BXI_DEV
-        else if (factor == 2) BXI_DYN1_F(2);
-        else if (factor == 1) BXI_DYN1_F(1);
-#endif
         else BXI_DYN1_F(0);
 #undef BXI_DYN1_F
 #undef BXI_DYN1

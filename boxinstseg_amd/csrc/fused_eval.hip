@@ -47,6 +47,7 @@
 // 2x800x1024), column / row partial maxima, 16-byte table entries.
 #include "loss_common.hpp"
 #include "dynamic_head_device.hpp"
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -78,12 +79,9 @@ constexpr unsigned int kMaxTag = 0x0fffffffu;   // tags are 28 bits (a predicate
 constexpr int kAcc2Split = 8, kAcc2Stride = 16; // tile arrivals: eight words per instance, each in its own 128 bytes
 constexpr int kAcc1Words = 64;                  // count-wave arrivals + sum W: 64 words, each in its own 128 bytes
 constexpr int kMaxInst = 65536;
-#ifndef BXI_ONE_OCC
-#define BXI_ONE_OCC 4
-#endif
-#ifndef BXI_LONG_OCC
-#define BXI_LONG_OCC 3      // workgroups per CU of the 8-row single-launch forms (138 VGPRs; a developer build may force 4: profiles/NOTES.md R6-3)
-#endif
+constexpr int kOneOcc = 4;                      // workgroups per CU of the single-launch form (<= 128 VGPRs: the tile role's budget)
+constexpr int kLongOcc = 3;                     // workgroups per CU of the 8-row single-launch forms (138 VGPRs: profiles/NOTES.md R6-3)
+constexpr int kPrepOcc = 5;                     // workgroups per CU of the two-launch form's first launch (prep_kernel: <= 96 VGPRs)
 // developer builds (-DBXI_WAITLOG): the longest wait of every bounded in-grid wait, by site, in polls -- which wait a slow launch sat in
 #ifdef BXI_WAITLOG
 static __device__ unsigned int g_waitlog[16];
@@ -91,7 +89,6 @@ static __device__ unsigned int g_waitlog[16];
 #else
 #define BXI_WL(site, spins) do {} while (0)
 #endif
-constexpr int kOneOcc = BXI_ONE_OCC;           // workgroups per CU of the single-launch form (<= 128 VGPRs: the tile role's budget)
 constexpr unsigned kFaultCounts = 1u, kFaultFinisher = 2u;
 // A wave whose bounded wait ran out says so on the evaluation's fault word (zeroed by the first table wave before the entries every waiter checks),
 // with a returning atomic it waits for BEFORE its arrival: the round in which the finisher sees the last arrival reads the fault word too.  The sum W
@@ -118,34 +115,9 @@ constexpr unsigned long long kCountFault = 1ull << 39, kSumwFault = 1ull << 62, 
 #define BXI_TW(kid, idx, ph) do {} while (0)
 #endif
 
-// developer build (-DBXI_ABLATE, tools/ablate.py): switch parts of the evaluation OFF (results become wrong) to see, without the
-// distortion of a trace, what the step time is sensitive to.  Never in the shipped library: BXI_AB(x) is the constant false there.
-#ifdef BXI_ABLATE
-static __device__ int g_ablate = 0;
-#define BXI_AB(bit) ((g_ablate & (bit)) != 0)
-#else
-#define BXI_AB(bit) false
-#endif
-
-// back-off between the polls of the bounded in-grid waits, in units of 64 clocks (tuning knobs; A/B of 1 .. 32 on one box moved the step by +-0.15 us at most: the waits are not what the launch ends on)
-#ifndef BXI_SLEEP_TAB
-#define BXI_SLEEP_TAB 16
-#endif
-#ifndef BXI_SLEEP_PRED
-#define BXI_SLEEP_PRED 16
-#endif
-#ifndef BXI_SLEEP_WORDS
-#define BXI_SLEEP_WORDS 8
-#endif
-#ifndef BXI_SLEEP_SUMW
-#define BXI_SLEEP_SUMW 8
-#endif
-#ifndef BXI_SLEEP_LEAD
-#define BXI_SLEEP_LEAD 4
-#endif
-#ifndef BXI_SLEEP_FIN
-#define BXI_SLEEP_FIN 2
-#endif
+// back-off between the polls of the bounded in-grid waits, in units of 64 clocks (A/B of 1 .. 32 on one box moved the step by +-0.15 us at most:
+// the waits are not what the launch ends on)
+constexpr int kSleepTab = 16, kSleepPred = 16, kSleepWords = 8, kSleepSumw = 8, kSleepLead = 4, kSleepFin = 2;
 
 #define BXI_RLX __ATOMIC_RELAXED
 #define BXI_AGENT __HIP_MEMORY_SCOPE_AGENT
@@ -485,7 +457,7 @@ __device__ __forceinline__ bool tab_entry(const Ws& ws, int m, bool want, int sp
             BXI_WL(1, spins);
             return true;
         }
-        __builtin_amdgcn_s_sleep(BXI_SLEEP_TAB);
+        __builtin_amdgcn_s_sleep(kSleepTab);
     }
     e = make_int4(0, 0, 0, 0);
     return false;
@@ -530,7 +502,7 @@ __device__ __forceinline__ void stream_block(const InstArgs& a, Ws& ws, float* _
     float* G = g_logits ? g_logits + (int64_t)n * P : nullptr;
     const float4 ninf = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 
-    if (G && !BXI_AB(16))   // zero-fill of d loss / d logits (depends on nothing); written through: drains while the launch is still reading
+    if (G)   // zero-fill of d loss / d logits (depends on nothing); written through: drains while the launch is still reading
         for (int cb = 0; cb < w; cb += kChunkC) {
             const int c = cb + lane * 4;
             if (c < w) {
@@ -548,7 +520,7 @@ __device__ __forceinline__ void stream_block(const InstArgs& a, Ws& ws, float* _
     {
         const int c = lane * 4;
 #pragma unroll
-        for (int i = 0; i < kSRows; ++i) v[i] = (r0 + i < r1 && c < w && !BXI_AB(64)) ? src(r0 + i, c) : ninf;
+        for (int i = 0; i < kSRows; ++i) v[i] = (r0 + i < r1 && c < w) ? src(r0 + i, c) : ninf;
     }
     after_loads(ws);
     BXI_TW(0, tix, 1);
@@ -654,7 +626,7 @@ __device__ __forceinline__ void pool_load(const PoolArgs& pa, int item, int segs
     const int64_t plane = (int64_t)pa.Hc * pa.Wc;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) v[ch] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < w && !BXI_AB(32)) {
+    if (c < w) {
         const float* base = pa.imgs + (int64_t)b * 3 * plane + (int64_t)(4 * r + wv) * pa.Wc + 4 * c;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -724,7 +696,7 @@ __device__ __forceinline__ void pool_block(const PoolArgs& pa, Ws& ws, int first
             for (int ch = 0; ch < 3; ++ch)
                 px[ch] = (part[(0 * 3 + ch) * 64 + lane] + part[(1 * 3 + ch) * 64 + lane] + part[(2 * 3 + ch) * 64 + lane] +
                           part[(3 * 3 + ch) * 64 + lane]) >> 4;
-            fch[wv * 64 + lane] = BXI_AB(1) ? 0.001 * (double)(px[0] + 2 * px[1] + 3 * px[2] + wv) : lab_f(lut, wv, px[0], px[1], px[2]);
+            fch[wv * 64 + lane] = lab_f(lut, wv, px[0], px[1], px[2]);
         }
         BXI_TW(0, tix, 3);
         lds_barrier();
@@ -966,7 +938,7 @@ __device__ __forceinline__ int pred_item(int h, int w, int n_ent, const ValidCel
                 BXI_WL(2, spins);
                 break;
             }
-            __builtin_amdgcn_s_sleep(BXI_SLEEP_PRED);
+            __builtin_amdgcn_s_sleep(kSleepPred);
         }
         if (!got) { ok = false; return 0; }
     } else {
@@ -1105,7 +1077,7 @@ __device__ __forceinline__ bool pred_words(const Ws& ws, const Tile& t, int h, i
         }
         if (__all(all)) { ok = true; BXI_WL(4, spins); break; }
         if (ws.pred_any) break;        // targets ready: the words are an EARLIER launch's -- what is not there now will not come (foreign or overwritten targets: loud at once, not after kSpinLimit polls)
-        __builtin_amdgcn_s_sleep(BXI_SLEEP_WORDS);
+        __builtin_amdgcn_s_sleep(kSleepWords);
     }
     return ok;        // false: the caller's arrival says so, and the finisher turns both losses into NaN
 }
@@ -1169,15 +1141,12 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
 #pragma unroll
     for (int j = 0; j < R; ++j) g[j] = 0.f;
     // per-pixel quantities of this lane and of the lane D to its right: before the wait, they need the logits only
-#ifndef BXI_PK_PAIRS
-#define BXI_PK_PAIRS 1
-#endif
     // PK (even dilation): rows 2k, 2k + 1 ride in the two halves of packed FP32 instructions (v_pk_mul / v_pk_fma: two pairs per instruction;
     // the conversions and the two transcendentals per pair stay scalar).  Every row's gradient receives the same terms in the same order.
     // 122 -> 106 registers at <2, 4>, 159 -> 138 at <2, 8>; 17.43 -> 17.07 us per evaluation at 32 instances (same box).  (The 8-row role
     // fits 113 registers when t and u are made again per pair -- four workgroups per CU --: slower, and the targets-ready long form then
     // stalled for seconds at 128 instances with every slot of the device taken from the start: profiles/NOTES.md R5-7.  Not built.)
-    constexpr bool PK = BXI_PK_PAIRS && D % 2 == 0 && RD % 2 == 0;
+    constexpr bool PK = D % 2 == 0 && RD % 2 == 0;
     typedef float v2 __attribute__((ext_vector_type(2)));
     float pa_[PK ? 1 : RD], pb_[PK ? 1 : RD], pt_[PK ? 1 : RD], pu_[PK ? 1 : RD], aR[PK ? 1 : RD], bR[PK ? 1 : RD], tR[PK ? 1 : RD], uR[PK ? 1 : RD];
     v2 pa2[PK ? RD / 2 : 1], pb2[PK ? RD / 2 : 1], pt2[PK ? RD / 2 : 1], pu2[PK ? RD / 2 : 1], aR2[PK ? RD / 2 : 1], bR2[PK ? RD / 2 : 1],
@@ -1209,8 +1178,7 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
     BXI_TW(1, tix, 2);
     if (!slow) {
         uint32_t pbyte[R + D];
-        if (BXI_AB(8)) { for (int i = 0; i < R + D; ++i) pbyte[i] = 0xfu; }
-        else if (early) {
+        if (early) {
             bool all = true;
 #pragma unroll
             for (int i = 0; i < R + D; ++i) { pbyte[i] = pearly[i]; all = all && (pbyte[i] >> 4) == 0u; }      // (words an earlier launch left carry tag 0)
@@ -1328,7 +1296,6 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
         } else {
 #pragma unroll
         for (int i = 0; i < R + D; ++i) {
-            if (BXI_AB(2)) break;
             const int j = i + D;
             if (i >= D) BXI_PAIR(i, i, i, aR, bR, tR, uR, 0, gq[i], gR[i])
             BXI_PAIR(i, j, i, aR, bR, tR, uR, 1, gq[j], gR[i])
@@ -1370,7 +1337,6 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
         }
         if (ONE && g_logits) bands_ok = f0e == ws.ep && f1e == ws.ep;
     }
-    if (BXI_AB(4)) { bands_ok = true; if (!have_scale) { have_scale = true; scale = 1e-6f; } }
     if (!have_scale || !bands_ok) {           // wave-uniform
         double total_w = 0.0;
         bool ok = false;
@@ -1387,7 +1353,7 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
             }
             bands_ok = f0 == ws.ep && f1 == ws.ep;
             if (have_scale && bands_ok) { ok = true; BXI_WL(5, spins); break; }
-            __builtin_amdgcn_s_sleep(BXI_SLEEP_SUMW);
+            __builtin_amdgcn_s_sleep(kSleepSumw);
         }
         bad |= !ok;
         have_scale = true;
@@ -1470,14 +1436,14 @@ __device__ __forceinline__ void leader_block(const InstArgs& a, int dil, Ws ws /
                 v = load16_past(ws.tab + n);
             if (lane >= ws.n_cb) f = ws.ep;
             if (__all(f == ws.ep && v.w == ws.ep)) { e = make_int4((int)v.x, (int)v.y, (int)v.z, (int)v.w); waited = true; BXI_WL(6, spins); break; }
-            __builtin_amdgcn_s_sleep(BXI_SLEEP_LEAD);
+            __builtin_amdgcn_s_sleep(kSleepLead);
         }
         for (int b0 = 64; b0 < ws.n_cb && waited; b0 += 64) {
             bool got = false;
             for (int spins = 0; spins <= spin_limit; ++spins) {
                 const unsigned int f = b0 + lane < ws.n_cb ? __hip_atomic_load(&ws.bandflag[(int64_t)n * ws.n_cb + b0 + lane], BXI_RLX, BXI_AGENT) : ws.ep;
                 if (__all(f == ws.ep)) { got = true; BXI_WL(7, spins); break; }
-                __builtin_amdgcn_s_sleep(BXI_SLEEP_LEAD);
+                __builtin_amdgcn_s_sleep(kSleepLead);
             }
             waited = got;
         }
@@ -1701,14 +1667,14 @@ __device__ __forceinline__ void finisher_role(const InstArgs& a, const Ws& ws, c
         for (int b0 = 0; b0 < N && ok; b0 += 64) {
             while (!dice_round(ws, N, b0, &dsum, &flt0)) {
                 if (++spins > spin_limit) { ok = false; break; }
-                __builtin_amdgcn_s_sleep(BXI_SLEEP_FIN);
+                __builtin_amdgcn_s_sleep(kSleepFin);
             }
         }
         if (zero_bit) total_w = total_weight_all_pairs(a, ws);
         else
             while (ok && !counts_complete(ws, n_items, &total_w, &flt0)) {
                 if (++spins > spin_limit) ok = false;
-                __builtin_amdgcn_s_sleep(BXI_SLEEP_FIN);
+                __builtin_amdgcn_s_sleep(kSleepFin);
             }
         BXI_WL(8, spins);
         if (lane == 0) { fin_f = dsum; fin_d[0] = total_w; fin_ok = ok ? 1 : 0; fin_flt = flt0 ? 1 : 0; }
@@ -1749,7 +1715,7 @@ __device__ __forceinline__ void finisher_role(const InstArgs& a, const Ws& ws, c
         const bool anyflt = __any(flt);
         if (lane == 0) { fin_i[wave] = arrived; fin_b[wave] = anyflt ? 1 : 0; }
         __syncthreads();
-        const bool all = (fin_i[0] + fin_i[1]) + (fin_i[2] + fin_i[3]) == n_tile_waves || BXI_AB(128);    // every tile wave arrives once, tiles or not
+        const bool all = (fin_i[0] + fin_i[1]) + (fin_i[2] + fin_i[3]) == n_tile_waves;    // every tile wave arrives once, tiles or not
         if ((fin_b[0] | fin_b[1]) | (fin_b[2] | fin_b[3])) fault_seen |= kFaultCounts;
         __syncthreads();
         if (all) break;
@@ -1821,7 +1787,7 @@ __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& v
                 BXI_WL(1, spins);
                 break;
             }
-            __builtin_amdgcn_s_sleep(BXI_SLEEP_TAB);
+            __builtin_amdgcn_s_sleep(kSleepTab);
         }
     } else {
         ok = tab_entry<ONE>(ws, lane, lane <= N, spin_limit, e0);
@@ -1847,7 +1813,6 @@ __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& v
     const bool may_arrive_early = ONE && ws.ep != kMaxTag;
     bool arrived = false;
     for (int ti = wid; ti < total && !bad; ti += nwaves) {
-        if (BXI_AB(256) && (ti & 7) == 7) continue;              // (ablation only: an eighth of the tiles gone -- what fewer tile waves would be worth)
         Tile t;
         if (!locate_tile<D, R, ONE>(ws, vc, N, e0, e1, ti, a.h, a.w, spin_limit, t)) { bad = true; break; }
         BXI_TW(1, wid, 1);
@@ -1867,9 +1832,7 @@ struct PrepTail {
 };
 
 // grid: [table blocks][pool blocks][stream blocks] (pool_first) or [table][stream][pool].  Nobody in this launch waits for anybody.
-// (Round 5 also built a FOLDED form -- predicate workgroups and the reducer at this launch's tail, under its logit stream -- and measured it
-// slower at every instance count, 37.9 vs 36.5 us at 128: profiles/NOTES.md R5-1.  Gone with ABI 7.)
-__global__ __launch_bounds__(256, 5) void prep_kernel(PoolArgs pa, int n_pool, int n_items, InstArgs a, int dil, int R, Ws ws_in, LossState st,
+__global__ __launch_bounds__(256, kPrepOcc) void prep_kernel(PoolArgs pa, int n_pool, int n_items, InstArgs a, int dil, int R, Ws ws_in, LossState st,
                                                        float* __restrict__ g_logits, int vec, int pool_first, PrepTail tl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Ws ws = ws_in;                                        // the tag is read where a role needs it (with_tag), behind its loads
@@ -1903,14 +1866,16 @@ __global__ __launch_bounds__(256, 5) void prep_kernel(PoolArgs pa, int n_pool, i
     BXI_TW(0, tix, 7);
 }
 
+// workgroups per CU of pair_kernel (four only where the tile role fits 128 VGPRs without spilling: dilation <= 2 -- every shipped configuration uses 2;
+// dilation 3 needs 10-row register arrays and ran with 9 spilled VGPRs at four per CU)
+constexpr int pair_occ(int D, int R) { return R == 4 ? (D <= 2 ? 4 : 3) : (D <= 2 ? 3 : 2); }
+
 // grid: [n_pb predicate blocks][reducer][N leaders][n_tb tile blocks][finisher].  The only waits: a tile wave for the predicate waves
 // (earlier in the grid, never waiting themselves), the finisher for everybody (nobody waits for it).  Every wait is bounded, and
 // running out of it is loud: NaN losses, status word, poisoned gradient (the reference surfaces launch failures through
 // AT_CUDA_CHECK, pairwise.cu:173,200).
 template <int D, int R>
-// (four workgroups per CU only where the tile role fits 128 VGPRs without spilling: dilation <= 2 -- every shipped configuration uses 2;
-// dilation 3 needs 10-row register arrays and ran with 9 spilled VGPRs at four per CU)
-__global__ __launch_bounds__(256, (R == 4 ? (D <= 2 ? 4 : 3) : (D <= 2 ? 3 : 2))) void pair_kernel(const float* __restrict__ up_prj, const float* __restrict__ up_pw, float warmup,
+__global__ __launch_bounds__(256, pair_occ(D, R)) void pair_kernel(const float* __restrict__ up_prj, const float* __restrict__ up_pw, float warmup,
                                                        float n2max, int zero_bit, int n_pb, int n_items, int spin_limit, ValidCells vc, float* __restrict__ losses,
                                                        float* __restrict__ g_logits, InstArgs a, Ws ws_in, LossState st) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1964,7 +1929,7 @@ __global__ __launch_bounds__(256, (R == 4 ? (D <= 2 ? 4 : 3) : (D <= 2 ? 3 : 2))
 // READY (BXI_EVAL_TARGETS_READY): an instantiation of its own -- no pool / predicate role, table workgroups at the head of the grid, sum W
 // gathered by the reducer workgroup -- so that the un-split kernel stays what it was (the same registers, no extra argument).
 template <int D, int R, bool READY>
-__global__ __launch_bounds__(256, (R == 4 ? kOneOcc : BXI_LONG_OCC)) void eval1_kernel(PoolArgs pa, int n_pool, int n_items, int n_pb, int n_tb, InstArgs a, Ws ws_in, LossState st, ValidCells vc,
+__global__ __launch_bounds__(256, (R == 4 ? kOneOcc : kLongOcc)) void eval1_kernel(PoolArgs pa, int n_pool, int n_items, int n_pb, int n_tb, InstArgs a, Ws ws_in, LossState st, ValidCells vc,
                                                         const float* __restrict__ up_prj, const float* __restrict__ up_pw, float warmup, float n2max, int spin_limit,
                                                         float* __restrict__ losses, float* __restrict__ g_logits, int vec, int merge, int ready_in, unsigned int key,
                                                         int n_tabw_in) {
@@ -2161,14 +2126,26 @@ __global__ __launch_bounds__(256) void rescale_kernel(InstArgs a, int dil, LossS
 __global__ void zero_losses2_kernel(float* losses, float* iter) { losses[0] = 0.f; losses[1] = 0.f; if (iter) atomicAdd(iter, 1.0f); }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-// Developer knobs (tools/ A/B scripts): read from the environment ONLY in a -DBXI_DEV build.  The shipped library reads nothing from the
-// process environment: what varies is an argument (`flags`), as include/boxinst_hip.h promises.
-#ifdef BXI_DEV
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-#define BXI_KNOB(name, dflt) ([&]() -> int { static const int set = getenv(name) ? 1 : 0; static const int v = env_int(name, 0); return set ? v : (dflt); }())
-#else
-#define BXI_KNOB(name, dflt) (dflt)
-#endif
+// LDS of a pool workgroup: the sRGB table and the three channels of its 64 pooled pixels (fp64), the four waves' partial sums
+constexpr size_t kPoolLds = sizeof(double) * (256 + 3 * 64) + sizeof(int) * 4 * 3 * 64;
+
+// pool workgroups for n_items items on `room` slots: as few items per workgroup as fill them, at most max_per (0: no cap; no room: max_per)
+static int pool_wgs(int n_items, int room, int max_per) {
+    int per = room > 0 ? (n_items + room - 1) / room : max_per;
+    if (max_per > 0 && per > max_per) per = max_per;
+    if (per < 1) per = 1;
+    return (n_items + per - 1) / per;
+}
+// predicate workgroups: one wave per item, at most `cap` workgroups
+static int pred_wgs(int n_items, int cap) {
+    const int n = (n_items + kWaves - 1) / kWaves;
+    return n < cap ? n : cap;
+}
+// tile workgroups: one wave per tile (`cap` tiles), at most `slots` workgroups
+static int tile_wgs(int64_t cap, int slots) {
+    const int64_t n = (cap + kWaves - 1) / kWaves;
+    return n < slots ? (int)n : slots;
+}
 
 // A stream that is being captured into a hipGraph: the launch is recorded, not run; what the host decides here is frozen into the graph
 static bool stream_is_capturing(hipStream_t s) {
@@ -2208,7 +2185,7 @@ static int stream_cus(hipStream_t s, int device_total) {
 // tiles on ~2500 tile waves: two rounds of a ~7 us dependent chain (table -> logits -> predicate words -> pair loop -> sum W -> adds).
 // 8-row tiles halve the count; at 157 - 161 VGPRs they run three workgroups per CU (round 3 ran them at two, where they lost): one
 // round.  Measured (two launches, 200 x 256 maps, same box): 96 instances 29.4 vs 30.1 us, 128: 35.9 vs 38.3, 256: 64.0 vs 69.7;
-// 64 instances: 24.2 vs 23.8 (single launch) -- hence the threshold.  BXI_TILE_ROWS / BXI_EVAL_TILE_ROWS_8 override.
+// 64 instances: 24.2 vs 23.8 (single launch) -- hence the threshold.  BXI_EVAL_TILE_ROWS_8 / BXI_EVAL_TILE_ROWS_4 override.
 static int tile_rows_for(int N, int dil) { return (N >= 96 && dil <= 2) ? 8 : 4; }
 
 // digest of what targets are computed FOR -- canvas, stride, window, threshold, per image its shape, rows removed and box count -- kept in
@@ -2262,13 +2239,6 @@ static HostPred host_pred(float thresh) {
     memcpy(&nb, &p.n2max, 4);
     cache.store(((uint64_t)tb << 32) | nb, std::memory_order_relaxed);
     return p;
-}
-
-template <int D, int R>
-static void launch_pair(hipStream_t s, int grid, size_t lds, const InstArgs& a, float warmup, float n2max, int zero_bit, int n_pb, int n_items, int spin_limit,
-                        const ValidCells& vc, const Ws& ws, const LossState& st, float* losses, float* g_logits, const float* up_prj, const float* up_pw) {
-    BXI_LAUNCH(n_pb > 0 ? "pair" : "pair_tiles", s, (pair_kernel<D, R>), dim3((unsigned)grid), dim3(256), lds, s, up_prj, up_pw, warmup, n2max, zero_bit,
-               n_pb, n_items, spin_limit, vc, losses, g_logits, a, ws, st);
 }
 
 size_t eval_ws_bytes(int B, int N, int h, int w) { return carve(nullptr, B, N, h, w, nullptr); }
@@ -2329,14 +2299,8 @@ int launch_targets(const bxi_image_batch* batch, const float* const* boxes_per_i
     const int n_items = (int)n_items64;
     const unsigned int key = targets_key(pa, batch->B, batch->Hc, batch->Wc, stride, dil, pr.n2max, gt.first);
     const bool pooled_in_launch = pool_vec_ok(batch, stride);
-    const int slots = 7 * device_cus();
-    int n_pool = 0;
-    if (pooled_in_launch) {
-        const int per = (n_items + slots - 1) / slots;
-        n_pool = (n_items + (per < 1 ? 1 : per) - 1) / (per < 1 ? 1 : per);
-    }
-    const size_t lds1 = sizeof(double) * (256 + 3 * 64) + sizeof(int) * 4 * 3 * 64;
-    BXI_LAUNCH("targets_pool", s, targets_pool_kernel, dim3((unsigned)(1 + n_pool)), dim3(256), lds1, s, pa, n_pool, n_items, gt, batch->Hc, batch->Wc, stride, h, w,
+    const int n_pool = pooled_in_launch ? pool_wgs(n_items, 7 * device_cus(), 0) : 0;      // (seven workgroups per CU: targets_pool_kernel)
+    BXI_LAUNCH("targets_pool", s, targets_pool_kernel, dim3((unsigned)(1 + n_pool)), dim3(256), kPoolLds, s, pa, n_pool, n_items, gt, batch->Hc, batch->Wc, stride, h, w,
                ws, key);
     rc = check_launch();
     if (rc != BXI_OK) return rc;
@@ -2349,8 +2313,7 @@ int launch_targets(const bxi_image_batch* batch, const float* const* boxes_per_i
         rc = check_launch();
         if (rc != BXI_OK) return rc;
     }
-    int n_pb = (n_items + kWaves - 1) / kWaves;
-    if (n_pb > 8 * device_cus()) n_pb = 8 * device_cus();
+    const int n_pb = pred_wgs(n_items, 8 * device_cus());
     BXI_LAUNCH("targets_pred", s, targets_pred_kernel, dim3((unsigned)n_pb), dim3(256), 0, s, h, w, G, vc, ws, dil, pr.n2max, n_pb, n_items);
     return check_launch();
 }
@@ -2404,15 +2367,12 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     // bit 0: 16-byte rows; bit 1: the logit stream is read non-temporally -- where the maps outgrow the L2 anyway (128 instances: 52 MB) the
     // stream's lines only push the Lab / predicate / table lines out of it: 37.4 -> 34.3 us per evaluation at 128 instances; at 32 (6.5 MB, which
     // the tile waves find in the L2 again) the hint costs 0.4 us.  profiles/NOTES.md R6-7
-    const int nt_stream = (int64_t)a.N * a.h * a.w * 4 >= ((int64_t)BXI_KNOB("BXI_NT_FROM_MB", kNtStreamFromMB) << 20) ? 2 : 0;
+    const int nt_stream = (int64_t)a.N * a.h * a.w * 4 >= ((int64_t)kNtStreamFromMB << 20) ? 2 : 0;
     const int vec = (((a.w & 3) == 0 && (reinterpret_cast<uintptr_t>(a.logits) & 15) == 0 &&
                       (!g_logits || (reinterpret_cast<uintptr_t>(g_logits) & 15) == 0)) ? 1 : 0) | nt_stream;
-    const int env_rows = BXI_KNOB("BXI_TILE_ROWS", 0);            // developer knobs (-DBXI_DEV builds only)
-    const int env_pool_first = BXI_KNOB("BXI_POOL_FIRST", 0);
-    const int env_pool_wgs = BXI_KNOB("BXI_POOL_WGS_PER_CU", 5);
-    const int force_rows = (flags & kFlagRows8) ? 8 : ((flags & kFlagRows4) ? 4 : env_rows);
-    const int R = force_rows == 4 || force_rows == 8 ? force_rows : tile_rows_for(a.N, dil);
-    if (eval_cap(a.N, a.h, a.w, dil, R) >= (1 << 24)) return BXI_ERR_BAD_SHAPE;     // the table packs a tile prefix into 24 bits
+    const int R = (flags & kFlagRows8) ? 8 : ((flags & kFlagRows4) ? 4 : tile_rows_for(a.N, dil));
+    const int64_t cap = eval_cap(a.N, a.h, a.w, dil, R);
+    if (cap >= (1 << 24)) return BXI_ERR_BAD_SHAPE;     // the table packs a tile prefix into 24 bits
     const HostPred pr = host_pred(color_thresh);
     if (ready && pr.zero_bit) return BXI_ERR_UNSUPPORTED;       // (bxi_boxinst_targets_f32 refuses thresholds <= 0 as well)
     ValidCells vc = {};
@@ -2422,118 +2382,77 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     const int n_items = (int)n_items64;
     const int spin_limit = (flags & kFlagGiveUp) ? -1 : kSpinLimit;
     const unsigned int key = ready ? targets_key(pa, batch->B, batch->Hc, batch->Wc, a.stride, dil, pr.n2max, a.gt.first) : 0u;
+    // what both forms are made of: table workgroups, stream workgroups (kSBlk rows of one instance map each), and the LDS of the
+    // stream / pool workgroups and of the tile waves / leaders
+    const int n_tab = ((a.N + 64) / 64 + kWaves - 1) / kWaves;
+    const int n_stream = a.N * ((a.h + kSBlk - 1) / kSBlk);
+    const size_t lds_stream = std::max(kPoolLds, 8 * (size_t)kWaves * a.w);
+    const size_t lds_pair = std::max(sizeof(float) * (size_t)kWaves * (R + 1) * 64, 2 * sizeof(float) * (size_t)(a.h + a.w) + 16);
+    const int cus = stream_cus(s, device_cus());                      // a CU-masked stream has fewer
+    const bool whole_device = cus >= device_cus();
 
     // ---- the single-launch form ---------------------------------------------------------------------------------------
-    const int env_one = BXI_KNOB("BXI_ONE_LAUNCH", 1);            // developer knob: 0 = always two launches
     // The single launch pays off while its front half (stream + pool workgroups) is resident at once: measured 24.8 vs 27.0 us at
     // 64 instances, 35.1 vs 33.9 at 96, 45.1 vs 39.4 at 128 (200 x 256 maps) -- hence: stream workgroups <= half the slots.
     const int one_slots = kOneOcc * device_cus();
-    const bool one_fits = 2 * (int64_t)a.N * ((a.h + kSBlk - 1) / kSBlk) <= one_slots && stream_cus(s, device_cus()) >= device_cus();
+    const bool one_fits = 2 * (int64_t)n_stream <= one_slots && whole_device;
     // (built for dilation <= 2: the single launch needs four workgroups per CU, and at dilation 3 the tile role does not fit 128 VGPRs)
     // Two shapes of the single launch: the SHORT form (4-row tiles, four workgroups per CU, the stream workgroups staying on as the first tile
     // workgroups) while its front half is resident at once; the LONG form (8-row tiles, three per CU, pool workgroups first, nobody waits for a
     // later workgroup) for many instances, where the short form's tile waves would each walk several tiles one after the other.
-    const bool whole_device = stream_cus(s, device_cus()) >= device_cus();
-    // Measured (2 x 800 x 1024, us per evaluation, one box): 128 instances long form 36.9 vs two launches 37.1, 96: 32.3 vs 31.6 -- no gain
-    // (three workgroups per CU slow the front half down by what the kernel boundary costs), so the library takes the long form only where it
-    // is asked to (BXI_EVAL_SINGLE_LAUNCH with 8-row tiles) and, with the targets ready (no front half to slow down), from kLongFrom on.
-    // With the targets ready the short form has table workgroups of its own at the head of the grid (eval1_kernel<D, R, true>): 14.4 vs 14.6 us
-    // for two launches at 32 instances, 18.6 vs 19.0 at 64 (as a duty of a stream wave behind its loads the table came ~5 us into the launch:
-    // 15.1 / 19.9).
-    // (Measured and dropped: a second launch that reads its predicate words by plain loads ahead of the logits and has sum W up front --
-    // 14.85 vs 14.65 at 32 instances, 31.9 vs 31.0 at 128: the tile role is bound by its arithmetic and memory pipeline, not by that hop.)
-    // (the long form exists with the targets ready only: with the image side in the launch it measured 36.9 vs 37.1 us for two launches at 128 instances,
-    // 32.3 vs 31.6 at 96 -- no gain -- and left the library with ABI 7: BXI_EVAL_SINGLE_LAUNCH | BXI_EVAL_TILE_ROWS_8 without targets runs two launches)
-    // (again in round 6, after the second launch had lost 6 us: the long form with the image side 31.0 vs 30.6 us at 128 instances, 27.8 vs 27.2 at 96 -- R6-14)
-    const bool long_form = R == 8 && dil <= 2 && ready && ((flags & kFlagSingle) || (a.N >= BXI_KNOB("BXI_LONG_FROM", kLongFrom) && whole_device && !(flags & kFlagShared)));
+    // The long form only with the targets ready: with the image side in the launch, three workgroups per CU slow the front half down by what
+    // the kernel boundary costs.  So the library takes it where it is asked to (BXI_EVAL_SINGLE_LAUNCH with 8-row tiles) and, with the targets
+    // ready, from kLongFrom on: 21.6 against 23.9 us for two launches (R6-14)
+    const bool long_form = R == 8 && dil <= 2 && ready && ((flags & kFlagSingle) || (a.N >= kLongFrom && whole_device && !(flags & kFlagShared)));
     // (targets ready: the short single launch while its stream workgroups are a quarter of the slots -- 14.1 vs 14.4-14.9 us for two launches at 32
-    // instances; at 64 two launches take 18.3 against 18.7 us, and from kLongFrom on the long form 21.6 against 23.9: R6-14)
-    const bool short_ok = one_fits && !(ready && (BXI_KNOB("BXI_READY_TWO", 0) || 4 * (int64_t)a.N * ((a.h + kSBlk - 1) / kSBlk) > one_slots));
-    if (env_one && !(flags & kFlagTwo) && (short_ok || env_one == 2 || (flags & kFlagSingle) || long_form) && !head && pooled_in_launch &&
-        (R == 4 || long_form) && dil <= 2 && !pr.zero_bit) {
-        const int env_one_pool = BXI_KNOB("BXI_ONE_POOL_WGS", 0);
-        const int Sn = (a.h + kSBlk - 1) / kSBlk;
-        const int n_stream = a.N * Sn;
-        const int slots = long_form ? BXI_LONG_OCC * device_cus() : one_slots;
-        // the front half (table, stream, pool) should fill the GPU exactly once: a pool workgroup takes several items
-        // (measured and dropped: pool workgroups alone filling the GPU first, predicate and stream workgroups behind them -- the
-        // stream workgroups, and with them the band flags and the leaders, then end 8 us late: 22.9 us per evaluation against 18.3)
-        // (also measured and dropped: stream waves that hold their loads back for 1 - 4 us so that the pool workgroups' reads go
-        // first: 18.0 / 18.3 / 20.3 us against 17.96; pool workgroups of one item each: 18.3)
+    // instances; at 64 two launches take 18.3 against 18.7 us: R6-14)
+    const bool short_ok = one_fits && !(ready && 4 * (int64_t)n_stream > one_slots);
+    const size_t lds_one = std::max(lds_stream, lds_pair);
+    if (!(flags & kFlagTwo) && (short_ok || (flags & kFlagSingle) || long_form) && !head && pooled_in_launch && (R == 4 || long_form) && dil <= 2 &&
+        !pr.zero_bit && lds_one <= 36 * 1024) {                       // (four workgroups per CU must fit)
+        const int slots = long_form ? kLongOcc * device_cus() : one_slots;
+        // the front half (table, stream, pool) should fill the GPU exactly once: a pool workgroup takes several items (never more than two in
+        // the long form, as in the first launch of the two-launch form below)
         const int front = slots - n_stream;
-        const int room = env_one_pool > 0 ? env_one_pool : (front > slots / 4 ? front : slots / 4);
-        int per = (n_items + room - 1) / room;
-        if (long_form && per > 2) per = 2;        // (never more than two items per pool workgroup: launch_fused_eval's first launch below)
-        const int n_pool = ready ? 0 : (n_items + (per < 1 ? 1 : per) - 1) / (per < 1 ? 1 : per);
-        int n_pb = ready ? 0 : (n_items + kWaves - 1) / kWaves;
-        if (n_pb > slots / 2) n_pb = slots / 2;
-        int64_t n_tb = (eval_cap(a.N, a.h, a.w, dil, R) + kWaves - 1) / kWaves;
-        // One tile per wave while the slots last: a wave that walks two tiles runs two ~7 us dependent chains one after the other.  (Round 4
-        // capped the tile workgroups at half the slots; they are the LAST workgroups of the grid and wait only for earlier ones, so nothing
-        // depends on their number -- 64 instances: 24.1 -> 22.9 us per evaluation, 32 instances unchanged: their 289 were below the cap.)
-        const int tb_cap = BXI_KNOB("BXI_ONE_TB_CAP", slots);
-        if (n_tb > tb_cap) n_tb = tb_cap;
+        const int n_pool = ready ? 0 : pool_wgs(n_items, front > slots / 4 ? front : slots / 4, long_form ? 2 : 0);
+        const int n_pb = ready ? 0 : pred_wgs(n_items, slots / 2);
+        // One tile per wave while the slots last: a wave that walks two tiles runs two ~7 us dependent chains one after the other.  The tile
+        // workgroups are the LAST workgroups of the grid and wait only for earlier ones, so nothing else depends on their number.
+        int n_tb = tile_wgs(cap, slots);
         // the stream workgroups stay on as the first tile workgroups (only while they leave half of the slots to the rest of the grid)
         // ... unless evaluations run on SEVERAL streams at once: each would hold its stream workgroups' slots while waiting, and three
         // or four of them leave no room for anybody's pool workgroups (measured: 2.4 ms per evaluation with four streams in flight,
         // against 10 us without the staying-on).  The library cannot see what else runs on the device and does not guess: the CALLER
         // says so (BXI_EVAL_SHARED_DEVICE; boxinstseg_amd/functional.py sets it once a second stream has been
         // seen on the device).  A launch that is being captured into a graph may be replayed next to anything: no staying-on either.
-        const int env_merge = BXI_KNOB("BXI_ONE_MERGE", 1);
         // ... and only while they are at most a QUARTER of the slots: at 64 instances (448 of 1024) the staying-on costs 0.3 us (21.65 vs 21.35 us, their
         // slots are what the pool workgroups -- three items each then -- are short of); at 32 instances it is worth 0.05 us (R6-12)
-        const int merge = env_merge && !long_form && one_fits && 4 * n_stream <= slots && !(flags & kFlagShared) && !stream_is_capturing(s) ? 1 : 0;
+        const int merge = !long_form && one_fits && 4 * n_stream <= slots && !(flags & kFlagShared) && !stream_is_capturing(s) ? 1 : 0;
         if (merge) n_tb = n_tb > n_stream ? n_tb - n_stream : 0;
-        size_t lds = sizeof(double) * (256 + 3 * 64) + sizeof(int) * 4 * 3 * 64;
-        if (lds < 8 * (size_t)kWaves * a.w) lds = 8 * (size_t)kWaves * a.w;
-        if (lds < sizeof(float) * (size_t)kWaves * (R + 1) * 64) lds = sizeof(float) * (size_t)kWaves * (R + 1) * 64;
-        if (lds < 2 * sizeof(float) * (size_t)(a.h + a.w) + 16) lds = 2 * sizeof(float) * (size_t)(a.h + a.w) + 16;
-        if (lds <= 36 * 1024) {                             // four workgroups per CU must fit
-            const int n_tabw = ready ? ((a.N + 64) / 64 + kWaves - 1) / kWaves : 0;
-            const unsigned grid = (unsigned)(n_tabw + n_stream + n_pool + n_pb + 1 + a.N + (int)n_tb + 1);
-#define BXI_ONE_CASE(DD)                                                                                                                    \
-            case DD:                                                                                                                        \
-                if (long_form)                                                                                                              \
-                    BXI_LAUNCH("eval1_ready", s, (eval1_kernel<DD, 8, true>), dim3(grid), dim3(256), lds, s, pa, n_pool, n_items, n_pb, (int)n_tb, a, ws, st, vc, \
-                               up_prj, up_pw, warmup, pr.n2max, spin_limit, losses, g_logits, vec, merge, ready, key, n_tabw);                  \
-                else if (ready)                                                                                                             \
-                    BXI_LAUNCH("eval1_ready", s, (eval1_kernel<DD, 4, true>), dim3(grid), dim3(256), lds, s, pa, n_pool, n_items, n_pb, (int)n_tb, a, ws, st, vc, \
-                               up_prj, up_pw, warmup, pr.n2max, spin_limit, losses, g_logits, vec, merge, ready, key, n_tabw);                  \
-                else                                                                                                                        \
-                    BXI_LAUNCH("eval1", s, (eval1_kernel<DD, 4, false>), dim3(grid), dim3(256), lds, s, pa, n_pool, n_items, n_pb, (int)n_tb, a, ws, st, vc, \
-                               up_prj, up_pw, warmup, pr.n2max, spin_limit, losses, g_logits, vec, merge, ready, key, n_tabw);                  \
-                break;
-            switch (dil) { BXI_ONE_CASE(1) BXI_ONE_CASE(2) default: return BXI_ERR_UNSUPPORTED; }
-#undef BXI_ONE_CASE
-            return check_launch();
-        }
+        const int n_tabw = ready ? n_tab : 0;
+        const unsigned grid = (unsigned)(n_tabw + n_stream + n_pool + n_pb + 1 + a.N + n_tb + 1);
+        constexpr decltype(&eval1_kernel<1, 8, true>) eval1_kernels[2][3] = {{eval1_kernel<1, 8, true>, eval1_kernel<1, 4, true>, eval1_kernel<1, 4, false>},
+                                                                             {eval1_kernel<2, 8, true>, eval1_kernel<2, 4, true>, eval1_kernel<2, 4, false>}};
+        BXI_LAUNCH(ready ? "eval1_ready" : "eval1", s, eval1_kernels[dil - 1][long_form ? 0 : (ready ? 1 : 2)], dim3(grid), dim3(256), lds_one, s, pa, n_pool, n_items, n_pb, n_tb, a, ws, st, vc, up_prj,
+                   up_pw, warmup, pr.n2max, spin_limit, losses, g_logits, vec, merge, ready, key, n_tabw);
+        return check_launch();
     }
 
     // ---- launch 1 --------------------------------------------------------------------------------------------------
-    const int n_tab = ((a.N + 64) / 64 + kWaves - 1) / kWaves;
-    const int Sn = (a.h + kSBlk - 1) / kSBlk;
-    const int n_stream = a.N * Sn;
-    // one item = the 4 input rows of 64 pooled pixels.  The whole launch should be resident at once (5 workgroups per CU at
+    // one item = the 4 input rows of 64 pooled pixels.  The whole launch should be resident at once (kPrepOcc workgroups per CU at
     // <= 96 VGPRs): a pool workgroup takes several items, the next one's loads in flight, when it is not.
-    const int room = env_pool_wgs * device_cus() - n_tab - (head ? 0 : n_stream);
     // ... but never more than two items per pool workgroup: its items are a dependent chain (load -> sums -> Lab -> store, ~2.5 us each), and
     // with many instances -- 896 stream workgroups at 128 -- the few pool workgroups the slots leave would each drag four or five of them
     // behind the HBM stream (the first launch's last 5 us at 128 instances).  Then the launch exceeds the slots and its tail workgroups
     // take them as they come free; the pool workgroups go FIRST in that case, the image side being the longer chain.  Measured: 40.1 ->
-    // 38.5 us per evaluation at 128 instances, 75.8 -> 70.3 at 256 (BXI_PREP_ITEMS=<n>: developer override)
-    const int env_prep_items = BXI_KNOB("BXI_PREP_ITEMS", 0);
-    int per = env_prep_items > 0 ? env_prep_items : (room > 0 ? (n_items + room - 1) / room : 8);
-    if (env_prep_items <= 0 && per > 2) per = 2;
-    const int n_pool = pooled_in_launch && !ready ? (n_items + (per < 1 ? 1 : per) - 1) / (per < 1 ? 1 : per) : 0;
+    // 38.5 us per evaluation at 128 instances, 75.8 -> 70.3 at 256
+    const int prep_slots = kPrepOcc * device_cus();
+    const int n_pool = pooled_in_launch && !ready ? pool_wgs(n_items, prep_slots - n_tab - (head ? 0 : n_stream), 2) : 0;
     PrepTail tl = {};
     tl.ready = ready; tl.key = key;
-    const int pool_first = env_pool_first || (!head && n_tab + n_stream + n_pool > env_pool_wgs * device_cus()) ? 1 : 0;
-    size_t lds1 = sizeof(double) * (256 + 3 * 64) + sizeof(int) * 4 * 3 * 64;
+    const int pool_first = !head && n_tab + n_stream + n_pool > prep_slots ? 1 : 0;
     // every refusal comes BEFORE the first launch: a refused call has enqueued nothing (callers fall back to other entry points)
-    size_t lds2 = sizeof(float) * (size_t)kWaves * (R + 1) * 64;
-    const size_t lds_leader = 2 * sizeof(float) * (size_t)(a.h + a.w) + 16;
-    if (lds2 < lds_leader) lds2 = lds_leader;
-    if (lds2 > 64 * 1024) return BXI_ERR_UNSUPPORTED;
+    if (lds_pair > 64 * 1024) return BXI_ERR_UNSUPPORTED;
     if (head && head_C != 8 && head_C != 16) return BXI_ERR_UNSUPPORTED;
     if (head) {
         // the head-fused first launch (factor 2, vector rows): tables, pool blocks, head tiles
@@ -2542,25 +2461,17 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
         const int tiles = ((head->H + kHeadR - 1) / kHeadR) * ((head->W + kYC - 1) / kYC);
         ws.n_cb = (head->H + kHeadR - 1) / kHeadR;
         ws.n_rp = (head->W + kYC - 1) / kYC;
-        const size_t lds_head = 8 * 4 * 64 + sizeof(float) * (2 * kHeadR * 64 + 512);
-        if (lds1 < lds_head) lds1 = lds_head;
-        if (lds1 > 64 * 1024) return BXI_ERR_UNSUPPORTED;
+        const size_t lds_head = std::max(kPoolLds, 8 * 4 * 64 + sizeof(float) * (2 * kHeadR * 64 + 512));
+        if (lds_head > 64 * 1024) return BXI_ERR_UNSUPPORTED;
         float* logits_out = const_cast<float*>(a.logits);
-        const unsigned grid1 = (unsigned)(n_tab + n_pool + a.N * tiles);
-#define BXI_HEAD_LAUNCH(CC, RR)                                                                                                          \
-        BXI_LAUNCH("head_prep", s, (head_prep_kernel<CC, RR>), dim3(grid1), dim3(256), lds1, s, pa, n_pool, n_items, a, dil, R, ws, st,     \
-                   g_logits, *head, head->params, logits_out, ready, key)
-        if (head_C == 16 && head->rel) BXI_HEAD_LAUNCH(16, true);
-        else if (head_C == 16) BXI_HEAD_LAUNCH(16, false);
-        else if (head_C == 8 && head->rel) BXI_HEAD_LAUNCH(8, true);
-        else if (head_C == 8) BXI_HEAD_LAUNCH(8, false);
-        else return BXI_ERR_UNSUPPORTED;
-#undef BXI_HEAD_LAUNCH
+        constexpr decltype(&head_prep_kernel<16, true>) head_kernels[2][2] = {{head_prep_kernel<16, true>, head_prep_kernel<16, false>},
+                                                                              {head_prep_kernel<8, true>, head_prep_kernel<8, false>}};
+        BXI_LAUNCH("head_prep", s, head_kernels[head_C == 8][head->rel ? 0 : 1], dim3((unsigned)(n_tab + n_pool + a.N * tiles)), dim3(256), lds_head, s, pa, n_pool, n_items, a, dil, R, ws,
+                   st, g_logits, *head, head->params, logits_out, ready, key);
     } else {
-        if (lds1 < 8 * (size_t)kWaves * a.w) lds1 = 8 * (size_t)kWaves * a.w;
-        if (lds1 > 64 * 1024) return BXI_ERR_UNSUPPORTED;
-        BXI_LAUNCH(ready ? "prep_ready" : "prep", s, prep_kernel, dim3((unsigned)(n_tab + n_stream + n_pool)), dim3(256), lds1, s, pa, n_pool, n_items, a, dil,
-                   R, ws, st, g_logits, vec, pool_first, tl);
+        if (lds_stream > 64 * 1024) return BXI_ERR_UNSUPPORTED;
+        BXI_LAUNCH(ready ? "prep_ready" : "prep", s, prep_kernel, dim3((unsigned)(n_tab + n_stream + n_pool)), dim3(256), lds_stream, s, pa, n_pool,
+                   n_items, a, dil, R, ws, st, g_logits, vec, pool_first, tl);
     }
     rc = check_launch();
     if (rc != BXI_OK) return rc;
@@ -2579,33 +2490,19 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     }
 
     // ---- launch 2 --------------------------------------------------------------------------------------------------
-    const int64_t cap = eval_cap(a.N, a.h, a.w, dil, R);
-    int64_t n_tb = (cap + kWaves - 1) / kWaves;
-    // the tile list's length is device data: the tile waves stride through it.  The launch should be resident in one round:
-    // 4 (R = 4: <= 128 VGPRs) or 2 (R = 8) workgroups per CU; the predicate waves are short-lived.
-    const int env_pair_wgs = BXI_KNOB("BXI_PAIR_WGS_PER_CU", 0);
-    const int occ = env_pair_wgs > 0 ? env_pair_wgs : (R == 4 ? (dil <= 2 ? 4 : 3) : (dil <= 2 ? 3 : 2));
+    // the tile list's length is device data: the tile waves stride through it.  The launch should be resident in one round
+    // (pair_occ workgroups per CU); the predicate waves are short-lived.
     // (the leaders are short-lived and are not counted; with them subtracted, 512 instances at two workgroups per CU left ONE
     // predicate workgroup for the whole image side: 4.4 ms per evaluation)
-    const int cus2 = stream_cus(s, device_cus());                      // a CU-masked stream has fewer
-    const int slots = occ * cus2 > 64 ? occ * cus2 : 64;
-    int n_pb = ready ? 0 : (n_items + kWaves - 1) / kWaves;  // (targets ready: the image side is in memory at this kernel's start)
-    if (n_pb > slots / 2) n_pb = slots / 2;     // (5 / 8 of the slots -- every item a wave of its own at 2 x 800 x 1024 and three per CU --: no difference, R6-10)
+    const int slots = pair_occ(dil, R) * cus > 64 ? pair_occ(dil, R) * cus : 64;
+    const int n_pb = ready ? 0 : pred_wgs(n_items, slots / 2);   // (targets ready: the image side is in memory at this kernel's start; R6-10)
     // (the predicate workgroups are short-lived: the tile workgroups behind them in the grid take their slots as they leave, so the
-    // tile workgroups are sized for the slots, not for what the predicate workgroups leave over -- BXI_PAIR_TB_FULL=0: the round-3 sizing)
-    const int env_tb_full = BXI_KNOB("BXI_PAIR_TB_FULL", 1);
-    if (n_tb > (env_tb_full ? slots : slots - n_pb)) n_tb = env_tb_full ? slots : slots - n_pb;
-    const int grid = n_pb + 1 + a.N + (int)n_tb + 1;      // predicate blocks + the reducer + leaders + tile blocks + the finisher
-#define BXI_PAIR_CASE(DD)                                                                                                                  \
-    case DD:                                                                                                                               \
-        if (R == 4) launch_pair<DD, 4>(s, grid, lds2, a, warmup, pr.n2max, pr.zero_bit, n_pb, n_items, spin_limit, vc, ws, st, losses, g_logits, up_prj, up_pw); \
-        else launch_pair<DD, 8>(s, grid, lds2, a, warmup, pr.n2max, pr.zero_bit, n_pb, n_items, spin_limit, vc, ws, st, losses, g_logits, up_prj, up_pw);        \
-        break;
-    switch (dil) {
-        BXI_PAIR_CASE(1) BXI_PAIR_CASE(2) BXI_PAIR_CASE(3) BXI_PAIR_CASE(4)
-        default: return fail(BXI_ERR_UNSUPPORTED);
-    }
-#undef BXI_PAIR_CASE
+    // tile workgroups are sized for the slots, not for what the predicate workgroups leave over)
+    const int grid = n_pb + 1 + a.N + tile_wgs(cap, slots) + 1;      // predicate blocks + the reducer + leaders + tile blocks + the finisher
+    constexpr decltype(&pair_kernel<1, 4>) pair_kernels[4][2] = {{pair_kernel<1, 4>, pair_kernel<1, 8>}, {pair_kernel<2, 4>, pair_kernel<2, 8>},
+                                                                 {pair_kernel<3, 4>, pair_kernel<3, 8>}, {pair_kernel<4, 4>, pair_kernel<4, 8>}};
+    BXI_LAUNCH(n_pb > 0 ? "pair" : "pair_tiles", s, pair_kernels[dil - 1][R == 8], dim3((unsigned)grid), dim3(256), lds_pair, s, up_prj, up_pw, warmup,
+               pr.n2max, pr.zero_bit, n_pb, n_items, spin_limit, vc, losses, g_logits, a, ws, st);
     rc = check_launch();
     return rc == BXI_OK ? rc : fail(rc);
 }
@@ -2629,18 +2526,8 @@ int launch_rescale_nhw(int N, int h, int w, const float* g_prj, const float* g_p
 
 int launch_rescale(const bxi_instances* in, const float* g_prj, const float* g_pw, int dil, const void* state, float* g_logits, void* stream) {
     InstArgs a;
-    int rc = fill_inst(in, a);
-    if (rc != BXI_OK) return rc;
-    if (!fused_eval_supported(dil)) return BXI_ERR_UNSUPPORTED;
-    if (a.N == 0) return BXI_OK;
-    if (!g_prj || !g_pw || !state || !g_logits) return BXI_ERR_NULL_POINTER;
-    if (a.N > 65535) return BXI_ERR_BAD_SHAPE;
-    if (reinterpret_cast<uintptr_t>(state) & 255) return BXI_ERR_WORKSPACE;
-    LossState st = {};
-    carve_state(const_cast<void*>(state), a.N, a.h, a.w, &st);
-    hipStream_t s = as_stream(stream);
-    BXI_LAUNCH("rescale", s, rescale_kernel, dim3(8, a.N), dim3(256), 0, s, a, dil, st, g_prj, g_pw, g_logits);
-    return check_launch();
+    const int rc = fill_inst(in, a);
+    return rc != BXI_OK ? rc : launch_rescale_nhw(a.N, a.h, a.w, g_prj, g_pw, dil, state, g_logits, stream);
 }
 
 }  // namespace bxi
@@ -2651,9 +2538,6 @@ extern "C" int bxi_debug_waitlog(unsigned int* out16, int reset) {   // develope
     if (rc == 0 && reset) { unsigned int z[16] = {0}; rc = (int)hipMemcpyToSymbol(HIP_SYMBOL(bxi::g_waitlog), z, sizeof(z)); }
     return rc;
 }
-#endif
-#ifdef BXI_ABLATE
-extern "C" int bxi_debug_set_ablate(int bits) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(bxi::g_ablate), &bits, sizeof(bits)); }
 #endif
 #ifdef BXI_TRACE
 extern "C" int bxi_debug_set_trace2(void* buf) {   // developer builds only

@@ -421,8 +421,8 @@ __global__ __launch_bounds__(256) void pairwise3_bwd_kernel(const T* __restrict_
 //             number): 8 x float4 stores per thread, aligned, no partner stores, no edge cases; the second evaluation of a pair
 //             is two multiply-adds and one v_log_f32 against 4 x fewer store instructions;
 //   backward  every UNORDERED pair once (further down).  Rounds 3-5 summed d f/d x_p over all eight taps in the pixel itself: 16 float4
-//             loads per thread, every gradient element fetched twice (tools/micro/pw_bwd_wide_ref.inc keeps that kernel as the
-//             measuring stick: 19.4 us where the pair kernel takes 13.8 and a copy of the bytes 12.7, same box, cold).
+//             loads per thread, every gradient element fetched twice: 19.4 us where the pair kernel takes 13.8 and a copy of the bytes
+//             12.7, same box, cold (profiles/NOTES.md R6-1).
 // The neighbours' probabilities of the four pixels overlap: 3 rows x (4 + 2d) staged entries are read once per thread.
 // A tile with a logit beyond +-34 (S could underflow) takes a per-pixel log-space path straight from global memory, exactly
 // pairwise.cu:38-58 (block-uniform choice, no extra LDS).
@@ -530,18 +530,6 @@ __global__ __launch_bounds__(256) void pairwise3_fwd_wide_kernel(const float* __
     }
 }
 
-// developer trace of these kernels (-DBXI_PW_TRACE; tools/micro/pw_bwd.hip): wall-clock stamps collected in scalar registers, written by the
-// workgroup's first lane at the end -- no memory wait in the middle (BXI_T's pointer load would drain the requests in flight)
-#ifdef BXI_PW_TRACE
-static __device__ long long* g_pw_trace = nullptr;
-#define PWT_DECL long long pwt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define PWT(ph) do { long long t_; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); pwt_[ph] = t_; } while (0)
-#define PWT_FLUSH(kid) do { if (threadIdx.x == 0 && g_pw_trace) for (int ph_ = 0; ph_ < 8; ++ph_) g_pw_trace[((size_t)(kid) * 8192 + blockIdx.x) * 8 + ph_] = pwt_[ph_]; } while (0)
-#else
-#define PWT_DECL do {} while (0)
-#define PWT(ph) do {} while (0)
-#define PWT_FLUSH(kid) do {} while (0)
-#endif
 // ---- f32, size == 3, W % 4 == 0: every UNORDERED pair once ("pair" kernel) ---------------------------------------------------------
 // Letting every pixel evaluate all eight of its taps evaluates each pair {p, q} twice and fetches each element of the upstream gradient
 // twice (once as g[k][p], once as the partner term g[7-k][.] of a neighbour).  But the pair has ONE
@@ -563,9 +551,7 @@ static __device__ long long* g_pw_trace = nullptr;
 // Out-of-map neighbours are staged as x = 0 (s = s' = 1/2, t = 0 exactly): their pairs contribute 0 by arithmetic, G is forced to 0 by a select
 // (a NaN / inf elsewhere in the upstream gradient must not leak through a clamped address).  Sums per pixel: own four taps, then the row share,
 // then V, then E -- a fixed order, run-to-run identical.
-#ifndef BXI_PWP_OCC
-#define BXI_PWP_OCC 5
-#endif
+constexpr int kPwpOcc = 5;          // workgroups per CU of the pair kernel
 
 #define BXI_DPP_ROW_SHL1 0x101
 #define BXI_DPP_ROW_SHR1 0x111
@@ -615,7 +601,7 @@ template <int D, int XR> struct PwPairGeom {
 };
 
 template <int D, int XR>
-__global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(const float* __restrict__ logits, const float* __restrict__ g_pair, int H, int W,
+__global__ __launch_bounds__(256, kPwpOcc) void pairwise3_bwd_pair_kernel(const float* __restrict__ logits, const float* __restrict__ g_pair, int H, int W,
                                                                  float* __restrict__ g_logits, int xcd_swizzle) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pw_raw[];
     typedef PwPairGeom<D, XR> Gm;
@@ -663,8 +649,6 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
         asm volatile("" : "+s"(gb)); asm volatile("" : "+s"(lb));
     }
     const int plane = (int)P * 4;
-    PWT_DECL;
-    PWT(0);
     // ---- requests, in the order their data is needed (loads return in order), as few and as wide as they can be: beyond its bytes a launch
     // pays ~0.16 us per load instruction of a workgroup (profiles/NOTES.md R6-1) -- the first version of this kernel asked for the staged logits
     // and the edge pixels one dword at a time (15 + 16 instructions per thread) and ran 21.4 us where the same kernel without them took 13.7.
@@ -734,7 +718,6 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
     // while the registers of the requests above are being filled)
     int th = tid;
     asm volatile("" : "+v"(th));
-    PWT(1);
     const int lr = th / (TC / 4), lc = (th % (TC / 4)) * 4;
     const int r = r0 + lr, c = c0 + lc;
     const bool live = r < H && c < W;                                   // W % 4 == 0: the four pixels are in the map together
@@ -776,9 +759,7 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
         }
     }
     if ((th & 63) == 0) satw[th >> 6] = __any(sat) ? 1 : 0;
-    PWT(2);
     lds_barrier();                                                       // the staged tile is complete (the gradient requests stay in flight)
-    PWT(3);
     if (satw[0] | satw[1] | satw[2] | satw[3]) {                         // rare, block-uniform: log space, straight from global memory
         if (live) {
             float a4[4];
@@ -817,7 +798,6 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
             Es[(w * TRT + a) * 4 + i] = (sq - mq) * (G * fast_rcp(sp * sq + mp * mq));
         }
     }
-    PWT(4);
     // ---- the extra rows: one pixel per thread (wave = row, lane = column)
     float acc2 = 0.f;
     if (XR > 0) {
@@ -840,7 +820,6 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
         const float v2 = sh[2] + dpp_zero_n<BXI_DPP_WAVE_SHL1, D>(sh[1]) + dpp_zero_n<BXI_DPP_WAVE_SHR1, D>(sh[3]);
         if (lr2 + D < TRT) Vp[(lr2 + D) * TC + lc2] = v2;                 // wave-uniform
     }
-    PWT(5);
     // ---- four adjacent pixels, their four later pairs each.  Two stages -- the pairs within the row, then those with the row D below
     float acc[4];
     {
@@ -900,7 +879,6 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
         }
         if (XR >= D || lr + D < TRT) *reinterpret_cast<float4*>(Vp + (lr + D) * TC + lc) = make_float4(vd[0], vd[1], vd[2], vd[3]);
     }
-    PWT(6);
     lds_barrier();
     // ---- every pixel: own taps + the row share (above), + the share from the row above, + the shares from outside the tile (taps in order) ; x -u
     // (positions derived again from the thread index: nothing but the sums above stays in registers across the passes)
@@ -951,8 +929,6 @@ __global__ __launch_bounds__(256, BXI_PWP_OCC) void pairwise3_bwd_pair_kernel(co
             __builtin_nontemporal_store(-u * ((acc2 + v) + e), g_logits + n * P + (int64_t)(r0 + gr) * W + c0 + gc);
         }
     }
-    PWT(7);
-    PWT_FLUSH(1);
 }
 
 template <typename T>
@@ -1041,7 +1017,7 @@ static int launch_bwd(const T* logits, const T* g_pair, int N, int H, int W, int
                     constexpr int kTR = 16, kTC = 64, kXR = 256 / kTC;
                     const int64_t cols_b = (W + kTC - 1) / kTC;
                     const int64_t t16 = (int64_t)N * ((H + kTR - 1) / kTR) * cols_b, t20 = (int64_t)N * ((H + kTR + kXR - 1) / (kTR + kXR)) * cols_b;
-                    const int64_t slots_b = (int64_t)BXI_PWP_OCC * device_cus();
+                    const int64_t slots_b = (int64_t)kPwpOcc * device_cus();
                     const int64_t c16 = ((t16 + slots_b - 1) / slots_b) * kTR, c20 = ((t20 + slots_b - 1) / slots_b) * (kTR + kXR);
                     const int64_t p16 = (int64_t)((H + kTR - 1) / kTR) * kTR, p20 = (int64_t)((H + kTR + kXR - 1) / (kTR + kXR)) * (kTR + kXR);
                     const bool tall = c20 < c16 || (t16 <= slots_b && t20 <= slots_b && p20 < p16);

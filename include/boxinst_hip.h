@@ -23,8 +23,7 @@
  *     shim turns a non-zero status into RuntimeError.
  *   - re-entrant, no process-wide mutable state, and nothing is read from the process environment: what varies is an
  *     argument (`flags` of the evaluation).  The few developer hooks (launch bracketing for benchmarks, a test switch of
- *     the tree filter) are declared in boxinst_hip_dev.h, not here; the A/B knobs of tools/ exist only in a -DBXI_DEV
- *     build.  One host thread per device is the expected use.
+ *     the tree filter) are declared in boxinst_hip_dev.h, not here.  One host thread per device is the expected use.
  *   - tensors are dense, row-major (NCHW like the reference), fp32 unless the name says _f64.
  */
 #ifndef BOXINST_HIP_H

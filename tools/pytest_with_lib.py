@@ -6,5 +6,6 @@ from boxinstseg_amd import build as hb
 hb.LIB_PATH = os.path.abspath(sys.argv[1])
 hb.is_stale = lambda: False
 hb.build = lambda force=False, verbose=False: hb.LIB_PATH
-import pytest
-sys.exit(pytest.main(sys.argv[2:]))
+if __name__ == '__main__':      # a test's spawned worker runs this file again as __mp_main__: it takes the library, not another session
+    import pytest
+    sys.exit(pytest.main(sys.argv[2:]))

@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Developer tool (GPU box): per-wave phase stamps (100 MHz wall clock) of ONE evaluation in a given form, any instance count.
 Needs the -DBXI_TRACE build (full stamps; add -DBXI_TRACE_LIGHT for first / last only):
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DBXI_TRACE -mllvm -amdgpu-kernarg-preload-count=16 \
-        -o boxinstseg_amd/lib/libboxinst_hip_trace.so boxinstseg_amd/csrc/*.hip
+  tools/build_variant.sh fused_eval.hip boxinstseg_amd/lib/libboxinst_hip_trace.so -DBXI_TRACE
   IPB=4 BXI_FLAGS=34 python tools/trace_forms.py         (flags: include/boxinst_hip.h BXI_EVAL_*; 32 = targets ready)
 Phases of a tile wave: 0 start, 1 tile located, 2 logits in + per-pixel done, 3 predicate words + masks, 5 pair loop done, 4 sum W / bands seen,
 6 adds issued, 7 arrived.  Stream / pool waves: 0 start, 1 loads in, 2..4 reductions / barriers, 7 end."""
@@ -14,8 +13,6 @@ hb.LIB_PATH = os.path.join(hb.LIB_DIR, os.environ.get('TRACE_LIB', 'libboxinst_h
 from boxinstseg_amd import functional as Fh, synthetic
 lib = _lib.load()
 lib.bxi_debug_set_trace2.argtypes = [C.c_void_p]
-if os.environ.get('BXI_ABLATE_BITS'):      # a -DBXI_TRACE -DBXI_ABLATE build: the trace of the launch with parts switched off (tools/ablate.py's bits)
-    assert lib.bxi_debug_set_ablate(int(os.environ['BXI_ABLATE_BITS'])) == 0
 dev = torch.device('cuda:0')
 ones = torch.ones(2, device=dev)
 flags = int(os.environ.get('BXI_FLAGS', '0'))
