@@ -4,7 +4,8 @@ MI355X-native (gfx950 HIP kernels behind a C ABI; see include/boxinst_hip.h and 
 Public surface (mirrors the reference's for this path):
     pairwise_nlog                      <-> mmdet.ops.pairwise.pairwise_nlog
     pairwise_nlog_forward / _backward  <-> mmdet.ops.pairwise.pairwise_ext
-    CondInstMaskHead                   <-> mmdet.models.dense_heads.CondInstMaskHead (loss path)
+    CondInstMaskHead                   <-> mmdet.models.dense_heads.CondInstMaskHead (loss path, simple_test)
+    paste_masks, paste_masks_device    : the test-time mask post-processing of simple_test as one kernel
     boxinst_mask_loss, color_affinity, box_bitmasks : functional form of the same kernels
     MeanField, dice_loss, mil_loss     <-> mmdet.models.dense_heads.discobox_head
     BoxProjectionLoss, LevelsetLoss, LocalConsistencyModule, LCM <-> mmdet.models.losses
@@ -12,7 +13,7 @@ Public surface (mirrors the reference's for this path):
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
-from .dynamic import DynamicMaskHead, dynamic_mask_forward
+from .dynamic import DynamicMaskHead, dynamic_mask_forward, paste_masks, paste_masks_device
 from .mask_head import CondInstMaskHead
 from .discobox import MeanField, dice_loss, meanfield_forward, meanfield_kernel, mil_loss
 from .levelset import LCM, BoxProjectionLoss, LevelsetLoss, LocalConsistencyModule, region_levelset
@@ -21,7 +22,7 @@ from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
-           'boxinst_mask_loss', 'BoxInstMaskLoss', 'dynamic_mask_forward', 'DynamicMaskHead', 'color_affinity', 'box_bitmasks',
+           'boxinst_mask_loss', 'BoxInstMaskLoss', 'dynamic_mask_forward', 'DynamicMaskHead', 'paste_masks', 'paste_masks_device', 'color_affinity', 'box_bitmasks',
            'CondInstMaskHead', 'HEADS', 'build_head', 'load_config',
            'MeanField', 'meanfield_kernel', 'meanfield_forward', 'dice_loss', 'mil_loss',
            'BoxProjectionLoss', 'LevelsetLoss', 'region_levelset', 'LocalConsistencyModule', 'LCM', 'LOSSES', 'build_loss',

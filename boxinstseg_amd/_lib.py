@@ -93,6 +93,8 @@ SIGNATURES = {
     'bxi_dynamic_mask_backward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_size_t, c_void_p]),
+    'bxi_mask_paste_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p,
+                                  c_void_p]),
     'bxi_meanfield_kernel_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_float, C.c_float, C.c_float,
                                          c_void_p, c_void_p]),
     'bxi_meanfield_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),

@@ -271,26 +271,21 @@ class CondInstMaskHead(nn.Module):
 
     def simple_test(self, mask_feat, det_labels, det_params, det_coors, det_level_inds, img_metas, num_classes,
                     rescale=False):
-        """condinst_head.py:1234-1286: masks of the detections -> per image, per class lists of uint8 [h,w] arrays."""
-        import numpy as np
-        from .dynamic import aligned_bilinear
+        """condinst_head.py:1234-1286: masks of the detections -> per image, per class lists of uint8 [h,w] arrays.
+
+        ``forward`` makes the logits; ``dynamic.paste_masks`` (one HIP launch, ``csrc/mask_paste.hip``) does sigmoid,
+        ``aligned_bilinear``, the crop to ``img_shape``, the resize to ``ori_shape`` when ``rescale`` and the threshold, and the
+        masks come to the host in one copy.  No detections at all: empty lists, as the reference.  An image without detections
+        gets ONE entry of empty ``(0, H, W)`` arrays (the reference appends a second entry there: it has no ``continue`` at
+        :1268-1269)."""
+        from .dynamic import paste_masks
         counts = [int(p.size(0)) for p in det_params]
         if sum(counts) == 0:
             return [[[] for _ in range(num_classes)] for _ in img_metas]
         img_inds = torch.cat([torch.full((c,), i, dtype=torch.long, device=mask_feat.device) for i, c in enumerate(counts)])
         logits = self.forward(mask_feat, torch.cat(det_params), torch.cat(det_coors), torch.cat(det_level_inds), img_inds)
-        probs = aligned_bilinear(logits.sigmoid(), self.out_stride)
-        results = []
-        for cur, labels, meta in zip(probs.split(counts, dim=0), det_labels, img_metas):
-            ih, iw = meta['img_shape'][:2]
-            cur = cur[:, :, :ih, :iw]
-            if rescale and cur.size(0):
-                oh, ow = meta['ori_shape'][:2]
-                cur = torch.nn.functional.interpolate(cur, (oh, ow), mode='bilinear', align_corners=False)
-            masks = (cur.squeeze(1) > 0.5).cpu().numpy().astype(np.uint8)
-            lab = labels.detach().cpu().numpy()
-            results.append([masks[lab == c] for c in range(num_classes)])
-        return results
+        return paste_masks(logits, img_inds, torch.cat(list(det_labels)).to(mask_feat.device), img_metas, num_classes,
+                           out_stride=self.out_stride, rescale=rescale, counts=counts)
 
     # ---- targets ----------------------------------------------------------------------------------
     def get_targets(self, gt_bboxes, gt_masks, img, img_metas):

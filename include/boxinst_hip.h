@@ -358,6 +358,19 @@ int bxi_dynamic_mask_generic_backward_f32(const float* feat, int B, int C, int H
                                           int disable_rel_coors, const float* g_logits, float* g_feat, float* g_params,
                                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* CondInstMaskHead.simple_test (condinst_head.py:1259-1285) after forward: sigmoid -> aligned_bilinear(., factor) (:146-167)
+ * -> crop to img_shape -> bilinear to ori_shape when rescaling -> (p > threshold) as uint8.
+ * logits [N,1,h,w]; img_inds [N]; out_offsets [N] = byte offset of instance j's [out_h, out_w] mask in `masks`;
+ * image_dims_host [B][4] = crop_h, crop_w, out_h, out_w (B <= BXI_MAX_IMAGES). N == 0 is a no-op.
+ * Each resize indexes and weighs its taps as ATen's bilinear kernel does, in fp32 (align_corners=True for the first,
+ * False with a target size for the second; equal dims are the identity); not bit-exact to the torch composition (FMA
+ * contraction, expf), so a probability within ~1e-6 of the threshold may land on the other side.  Every byte of each
+ * instance's [out_h, out_w] block is written exactly once, no atomics; img_inds must lie in [0, B) (an instance outside
+ * is skipped) and the blocks inside `masks`.  Crops larger than factor * (h, w), dims < 1, B outside 1..64: BXI_ERR_BAD_SHAPE. */
+int bxi_mask_paste_u8(const float* logits, int N, int h, int w, int factor, const int64_t* img_inds,
+                      const int64_t* out_offsets, int B, const int32_t* image_dims_host, float threshold,
+                      uint8_t* masks, void* stream);
+
 /* ===========================================================================================
  * 5. DiscoBox pseudo-label path -- mmdet/models/dense_heads/discobox_head.py:
  *    MeanField.__init__ (:591-613), MeanField.forward / simple_forward (:617-655),
