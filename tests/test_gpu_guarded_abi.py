@@ -1,0 +1,540 @@
+"""The C ABI with everything guarded (run on a real MI355X: -m gpu).
+
+Every device input lies inside NaN / -1 bands at a chosen misalignment, every output and every "contents undefined" workspace / state
+inside a recognisable bit pattern (tests/guarded.py); the evaluation workspace is zeroed once, as the header demands, inside its bands.
+Every case asserts: return code 0 (and evaluation status 0), bands intact, outputs fully written, inputs unchanged, and the results
+against the family's ORACLE at the tolerance the family's existing test uses (TOL = 1e-4 of test_gpu_parity.py; 2e-6 / 1e-12 at op
+level; the tie rule of test_gpu_mask_paste.py).  On top, exact: the guarded call at lead 0 is bit-identical to the same call on plain
+fresh tensors -- same kernel, same data, so a difference means the kernel consumed something outside its input.
+
+A guard band cannot see a load whose value is selected away afterwards; it sees stores outside a tensor, elements nobody wrote, and
+out-of-bounds loads whose value reaches an output (NaN)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from boxinstseg_amd import synthetic
+from tests import guarded as G
+from tests.helpers import grad_report, oracle_path, rel
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+
+# entry point -> the test of this module that runs it guarded (tests/test_guarded_complete.py walks _lib.SIGNATURES)
+GUARDED = {
+    'bxi_pairwise_nlog_forward_f32': 'test_pairwise_forward_guarded',
+    'bxi_pairwise_nlog_forward_f64': 'test_pairwise_forward_guarded',
+    'bxi_pairwise_nlog_backward_f32': 'test_pairwise_backward_guarded',
+    'bxi_pairwise_nlog_backward_f64': 'test_pairwise_backward_guarded',
+    'bxi_boxinst_eval_f32': 'test_eval_guarded',
+    'bxi_boxinst_targets_f32': 'test_eval_guarded',
+    'bxi_boxinst_eval_workspace_init': 'test_eval_guarded',
+    'bxi_boxinst_grad_rescale_f32': 'test_eval_guarded',
+    'bxi_boxinst_grad_rescale_nhw_f32': 'test_eval_guarded',
+    'bxi_boxinst_loss_fwd_bwd_f32': 'test_loss_from_bits_guarded',
+    'bxi_boxinst_loss_backward_f32': 'test_loss_from_bits_guarded',
+    'bxi_color_affinity_f32': 'test_color_affinity_guarded',
+    'bxi_box_bitmasks_f32': 'test_box_bitmasks_guarded',
+    'bxi_mask_paste_u8': 'test_mask_paste_guarded',
+    'bxi_levelset_loss_forward_f32': 'test_levelset_guarded',
+    'bxi_levelset_loss_backward_f32': 'test_levelset_guarded',
+}
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+class _Hook:
+    """Kernel names of the launches inside the block (bxi_dev_set_launch_hook)."""
+
+    def __init__(self):
+        from boxinstseg_amd import _lib
+        self.names = []
+        self._lib = _lib
+        self._cb = _lib.LAUNCH_HOOK(lambda name, phase, st, user: self.names.append(name.decode()))
+
+    def __enter__(self):
+        self._lib.load().bxi_dev_set_launch_hook(C.cast(self._cb, C.c_void_p), None)
+        return self
+
+    def __exit__(self, *exc):
+        self._lib.load().bxi_dev_set_launch_hook(None, None)
+        return False
+
+
+# ---------------------------------------------------------------------------------------------
+# op level: pairwise_nlog
+# ---------------------------------------------------------------------------------------------
+# the first four: ADVICE.md's shapes for the pair backward (H <= D, one row: H = 1 leaves the pair kernel), so that the first and the
+# last instance lie next to the bands; then every dilation the kernels are built for and one above, W % 4 == 0 and not, W > one tile
+PW_CASES = [((3, 2, 8), 4), ((2, 3, 4), 4), ((3, 3, 8), 3), ((2, 1, 8), 1),
+            ((2, 13, 20), 1), ((2, 13, 20), 2), ((2, 13, 20), 3), ((2, 13, 20), 4), ((2, 13, 20), 6),
+            ((2, 9, 18), 1), ((2, 9, 18), 2), ((2, 9, 18), 3), ((2, 9, 18), 4), ((2, 9, 18), 6), ((1, 21, 72), 2)]
+PW_IDS = ['%dx%dx%d_d%d' % (s + (d,)) for s, d in PW_CASES]
+
+
+def _pw_data(shape, dil, np_dtype):
+    from oracle import c_oracle
+    rng = np.random.default_rng(31)
+    x = (rng.standard_normal(shape) * 3).astype(np_dtype)
+    want = c_oracle.pairwise_nlog_fwd(x, 3, dil)
+    gp = rng.standard_normal(want.shape).astype(np_dtype)
+    want_g = c_oracle.pairwise_nlog_bwd(x, want, gp, 3, dil)
+    return x, want, gp, want_g
+
+
+@pytest.mark.parametrize('dtype,tol', [(np.float32, 2e-6), (np.float64, 1e-12)], ids=['f32', 'f64'])
+@pytest.mark.parametrize('shape,dil', PW_CASES, ids=PW_IDS)
+def test_pairwise_forward_guarded(dev, dtype, tol, shape, dil):
+    """bxi_pairwise_nlog_forward_*: logits / out misaligned alone and together (pairwise_op.hip: `wide` looks at `out` only -- the side
+    'out misaligned, W % 4 == 0' and the side 'logits misaligned under the wide kernel' both run here)."""
+    from boxinstseg_amd import _lib
+    lib = _lib.load()
+    fn = lib.bxi_pairwise_nlog_forward_f32 if dtype == np.float32 else lib.bxi_pairwise_nlog_forward_f64
+    x, want, _, _ = _pw_data(shape, dil, dtype)
+    N, H, W = shape
+    band = G.plane_band(H, W, dil)
+    xt = torch.from_numpy(x[:, None]).to(dev)
+    plain = torch.empty((N, 8, H, W), dtype=xt.dtype, device=dev)
+    assert fn(xt.data_ptr(), N, H, W, 3, dil, plain.data_ptr(), _stream(dev)) == 0
+    leads = [(0, 0), (1, 0), (0, 1), (2, 0), (0, 3), (1, 3)] if dtype == np.float32 else [(0, 0), (1, 0), (0, 1), (1, 1)]
+    for lx, lo in leads:
+        gx = G.embed(xt, lx, band)
+        go = G.out((N, 8, H, W), xt.dtype, dev, lo, band)
+        assert fn(gx.ptr(), N, H, W, 3, dil, go.ptr(), _stream(dev)) == 0, (lx, lo)
+        G.check_bands(gx, go)
+        G.check_written(go)
+        G.check_unchanged(gx)
+        got = go.t.cpu().numpy()
+        assert np.abs(got - want).max() <= tol * max(1.0, np.abs(want).max()), (lx, lo)
+        if (lx, lo) == (0, 0):
+            assert torch.equal(go.t.view(torch.int32 if dtype == np.float32 else torch.int64),
+                               plain.view(torch.int32 if dtype == np.float32 else torch.int64)), 'lead 0 differs from the plain call'
+
+
+@pytest.mark.parametrize('dtype,tol', [(np.float32, 2e-6), (np.float64, 1e-12)], ids=['f32', 'f64'])
+@pytest.mark.parametrize('shape,dil', PW_CASES, ids=PW_IDS)
+def test_pairwise_backward_guarded(dev, dtype, tol, shape, dil):
+    """bxi_pairwise_nlog_backward_*: the pair kernel (f32, W % 4 == 0, H >= 2, dilation <= 4, all of logits | g_pair | g_logits 16-byte
+    aligned) and the gather kernel it leaves to whenever ONE of the three pointers is misaligned -- each alone, and all together."""
+    from boxinstseg_amd import _lib
+    lib = _lib.load()
+    fn = lib.bxi_pairwise_nlog_backward_f32 if dtype == np.float32 else lib.bxi_pairwise_nlog_backward_f64
+    x, pw, gp, want_g = _pw_data(shape, dil, dtype)
+    N, H, W = shape
+    band = G.plane_band(H, W, dil)
+    xt, pwt, gpt = torch.from_numpy(x[:, None]).to(dev), torch.from_numpy(pw).to(dev), torch.from_numpy(gp).to(dev)
+    ity = torch.int32 if dtype == np.float32 else torch.int64
+    plain = torch.empty_like(xt)
+    assert fn(xt.data_ptr(), pwt.data_ptr(), gpt.data_ptr(), N, H, W, 3, dil, plain.data_ptr(), _stream(dev)) == 0
+    if dtype == np.float32:
+        leads = [(0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1), (0, 0, 0, 2), (3, 0, 0, 0), (1, 2, 3, 1)]
+    else:
+        leads = [(0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1), (1, 1, 1, 1)]
+    for lx, lp, lg, lo in leads:
+        gx, gpw, ggp = G.embed(xt, lx, band), G.embed(pwt, lp, band), G.embed(gpt, lg, band)
+        go = G.out(xt.shape, xt.dtype, dev, lo, band)
+        assert fn(gx.ptr(), gpw.ptr(), ggp.ptr(), N, H, W, 3, dil, go.ptr(), _stream(dev)) == 0
+        G.check_bands(gx, gpw, ggp, go)
+        G.check_written(go)
+        G.check_unchanged(gx, gpw, ggp)
+        got = go.t.cpu().numpy()[:, 0]
+        assert np.isfinite(got).all(), (lx, lp, lg, lo)
+        assert np.abs(got - want_g).max() <= 10 * tol * max(1.0, np.abs(want_g).max()), (lx, lp, lg, lo)
+        if (lx, lp, lg, lo) == (0, 0, 0, 0):
+            assert torch.equal(go.t.view(ity), plain.view(ity)), 'lead 0 differs from the plain call'
+
+
+# ---------------------------------------------------------------------------------------------
+# the evaluation and what goes with it
+# ---------------------------------------------------------------------------------------------
+def _canvas(which):
+    """Two images, three boxes each, two instances per box: logits 24 x 40 (w % 4 == 0: the pointer alone decides) or 24 x 41 (it does not)."""
+    if which == 'w40':
+        return synthetic.make_batch(B=2, H=96, W=160, boxes_per_img=3, inst_per_box=2, seed=61, img_shapes=[(96, 131), (70, 160)],
+                                    ori_shapes=[(48, 66), (210, 480)], min_box=16, max_box=80)
+    return synthetic.make_batch(B=2, H=96, W=164, boxes_per_img=3, inst_per_box=2, seed=62, img_shapes=[(96, 133), (71, 164)],
+                                ori_shapes=[(48, 66), (210, 480)], min_box=16, max_box=80)
+
+
+EVAL_LEADS = {      # logits, g_logits, imgs, boxes (ONE concatenated tensor), gt_inds, losses, upstream scalars
+    'aligned': dict(),
+    'logits': dict(logits=1),
+    'g_logits': dict(g_logits=2),
+    'imgs': dict(imgs=1),
+    'boxes': dict(boxes=1),
+    'gt_inds': dict(gt_inds=1),
+    'losses': dict(losses=1),
+    'all': dict(logits=3, g_logits=1, imgs=2, boxes=3, gt_inds=1, losses=3, up=1),
+}
+
+
+class _EvalSet:
+    """One evaluation's buffers at the C ABI, all guarded."""
+
+    def __init__(self, d, dev, leads, lib, Fh, N_ws=None):
+        self.d = d
+        h, w = d['h'], d['w']
+        band = G.plane_band(h, w, 4)
+        L = lambda k: leads.get(k, 0)
+        self.logits = G.embed(torch.from_numpy(d['mask_logits']).to(dev), L('logits'), band)
+        self.imgs = G.embed(torch.from_numpy(d['imgs']).to(dev), L('imgs'), G.plane_band(d['H'], d['W'], 0))
+        self.gt_inds = G.embed(torch.from_numpy(d['gt_inds']).to(dev), L('gt_inds'), 64)
+        # the per-image box arrays as consecutive slices of ONE tensor, the way a collate function hands them over
+        allb = np.concatenate(d['gt_bboxes'], 0).astype(np.float32)
+        self.boxes = G.embed(torch.from_numpy(allb).to(dev), L('boxes'), 64)
+        cnt = [len(b) for b in d['gt_bboxes']]
+        first = np.concatenate([[0], np.cumsum(cnt)])
+        self.box_views = [self.boxes.t[first[i]:first[i + 1]] for i in range(len(cnt))]
+        self.up = G.embed(torch.tensor([0.5, 3.0], device=dev), L('up'), 64)
+        self.batch = Fh._Batch(self.imgs.t, d['img_metas'], 10)
+        self.inst = Fh._Inst(self.logits.t, self.gt_inds.t, self.box_views, d['H'], d['W'], d['stride'])
+        # (the wrappers' .contiguous() / .to() pass a contiguous view of the right type through unchanged: otherwise this would test copies)
+        assert self.batch.imgs.data_ptr() == self.imgs.ptr() and self.inst.logits.data_ptr() == self.logits.ptr()
+        assert self.inst.gt_inds.data_ptr() == self.gt_inds.ptr()
+        assert [b.data_ptr() for b in self.inst.boxes] == [v.data_ptr() for v in self.box_views]
+        N = self.inst.N
+        self.losses = G.out(2, torch.float32, dev, L('losses'), 64)
+        self.grad = G.out(self.logits.t.shape, torch.float32, dev, L('g_logits'), band)
+        self.state = G.out(lib.bxi_boxinst_loss_state_bytes(N, h, w), torch.uint8, dev, 0, 1024)       # 256-byte aligned by contract
+        self.ws = G.out(lib.bxi_boxinst_eval_workspace_bytes(d['B'], d['H'], d['W'], d['stride'], N_ws or N), torch.uint8, dev, 0, 1024)
+        # zeroed once, inside its bands, by the entry point the header names for it
+        rc = lib.bxi_boxinst_eval_workspace_init(self.ws.ptr(), self.ws.numel, _stream(dev))
+        assert rc == 0, rc
+        G.check_bands(self.ws)
+        assert int(self.ws.t.ne(0).sum()) == 0
+        self.status_off = lib.bxi_boxinst_loss_state_status_offset(N, h, w)
+
+    def inputs(self):
+        return [self.logits, self.imgs, self.gt_inds, self.boxes, self.up]
+
+    def status(self):
+        return int(self.state.t[self.status_off:self.status_off + 4].view(torch.int32).item())
+
+
+def _assert_eval_result(s, ref, what):
+    got = s.losses.t.cpu().numpy()
+    assert np.isfinite(got).all(), (what, got)
+    assert rel(float(got[0]), ref['loss_prj']) <= TOL, (what, got, ref['loss_prj'])
+    assert rel(float(got[1]), ref['loss_pairwise']) <= TOL or abs(float(got[1]) - ref['loss_pairwise']) < 1e-7, (what, got, ref['loss_pairwise'])
+    grad = s.grad.t.cpu().numpy()[:, 0]
+    assert np.isfinite(grad).all(), what
+    err, ties = grad_report(grad, ref['grad'], s.d['mask_logits'][:, 0])
+    assert err <= TOL, f'{what}: grad err {err:.3e} ({ties} ambiguous arg-max lines excluded)'
+
+
+EVAL_FORMS = ['default', 'single_launch', 'single_launch_shared_device', 'two_launches_4_row_tiles', 'two_launches_8_row_tiles', 'targets_ahead']
+
+
+@pytest.mark.parametrize('form', EVAL_FORMS)
+@pytest.mark.parametrize('canvas', ['w40', 'w41'])
+def test_eval_guarded(dev, canvas, form):
+    """bxi_boxinst_eval_f32 in every shipped form (the targets made ahead by bxi_boxinst_targets_f32 among them), then
+    bxi_boxinst_grad_rescale_f32 / _nhw_f32 to other upstream factors: logits, g_logits, imgs, the box arrays, gt_inds and losses
+    misaligned one at a time and together.  fused_eval.hip's `vec` (logits | g_logits) and color_affinity.hip's pool_vec_ok (imgs) take
+    their other side here with a width that would allow the vector path: misaligned images go through the generic pooling launches
+    (pack_lab4 is launched), aligned ones never."""
+    from boxinstseg_amd import _lib, functional as Fh
+    lib = _lib.load()
+    flags = {'default': 0, 'single_launch': _lib.EVAL_SINGLE_LAUNCH, 'single_launch_shared_device': _lib.EVAL_SINGLE_LAUNCH | _lib.EVAL_SHARED_DEVICE,
+             'two_launches_4_row_tiles': _lib.EVAL_TWO_LAUNCHES | _lib.EVAL_TILE_ROWS_4,
+             'two_launches_8_row_tiles': _lib.EVAL_TWO_LAUNCHES | _lib.EVAL_TILE_ROWS_8, 'targets_ahead': _lib.EVAL_TARGETS_READY}[form]
+    d = _canvas(canvas)
+    ref1 = oracle_path(d, warmup=0.37, want_targets=False)
+    ref2 = oracle_path(d, warmup=0.37, g_prj=0.5, g_pw=3.0, want_targets=False)
+    st = _stream(dev)
+
+    def evaluate(s, up):
+        if form == 'targets_ahead':
+            rc = lib.bxi_boxinst_targets_f32(C.byref(s.batch.struct), s.inst.struct.boxes_per_img_host, s.inst.struct.gt_count_host, d['stride'], 3, 2,
+                                             0.3, s.ws.ptr(), s.ws.numel, st)
+            assert rc == 0, _lib.status_string(rc)
+        rc = lib.bxi_boxinst_eval_f32(C.byref(s.batch.struct), C.byref(s.inst.struct), 3, 2, 0.3, 0.37, up[0], up[1], s.losses.ptr(), s.grad.ptr(),
+                                      s.state.ptr(), s.ws.ptr(), s.ws.numel, flags, st)
+        assert rc == 0, _lib.status_string(rc)
+
+    # the same call on plain fresh tensors: what lead 0 has to reproduce bit for bit
+    from tests.helpers import to_dev
+    t = to_dev(d, dev)
+    pb, pi = Fh._Batch(t['imgs'], d['img_metas'], 10), Fh._Inst(t['logits'], t['gt_inds'], t['gt_bboxes'], d['H'], d['W'], d['stride'])
+    p_losses, p_grad = torch.zeros(2, device=dev), torch.empty_like(t['logits'])
+    p_state = torch.empty(lib.bxi_boxinst_loss_state_bytes(pi.N, pi.h, pi.w), dtype=torch.uint8, device=dev)
+    p_ws = torch.zeros(lib.bxi_boxinst_eval_workspace_bytes(d['B'], d['H'], d['W'], d['stride'], pi.N), dtype=torch.uint8, device=dev)
+    if form == 'targets_ahead':
+        assert lib.bxi_boxinst_targets_f32(C.byref(pb.struct), pi.struct.boxes_per_img_host, pi.struct.gt_count_host, d['stride'], 3, 2, 0.3,
+                                           p_ws.data_ptr(), p_ws.numel(), st) == 0
+    assert lib.bxi_boxinst_eval_f32(C.byref(pb.struct), C.byref(pi.struct), 3, 2, 0.3, 0.37, None, None, p_losses.data_ptr(), p_grad.data_ptr(),
+                                    p_state.data_ptr(), p_ws.data_ptr(), p_ws.numel(), flags, st) == 0
+    torch.cuda.synchronize()
+
+    for name, leads in EVAL_LEADS.items():
+        what = f'{canvas} {form} {name}'
+        # unit upstream factors (NULL), then rescaled to (0.5, 3.0) by bxi_boxinst_grad_rescale_f32 / _nhw_f32
+        s = _EvalSet(d, dev, leads, lib, Fh)
+        with _Hook() as hk:
+            evaluate(s, (None, None))
+        torch.cuda.synchronize()
+        assert s.status() == 0, what
+        # the generic pooling launches exactly where the images are misaligned (stride 4, Wc % 4 == 0 in both canvases)
+        assert ('pack_lab4' in hk.names) == bool(leads.get('imgs', 0)), (what, hk.names)
+        G.check_bands(s.losses, s.grad, s.state, s.ws, *s.inputs())
+        G.check_written(s.losses, s.grad)
+        G.check_unchanged(*s.inputs())
+        _assert_eval_result(s, ref1, what)
+        if name == 'aligned':
+            assert torch.equal(s.losses.t.view(torch.int32), p_losses.view(torch.int32)), what
+            assert torch.equal(s.grad.t.view(torch.int32), p_grad.view(torch.int32)), what
+        if name in ('aligned', 'g_logits', 'all'):
+            if name == 'g_logits':
+                rc = lib.bxi_boxinst_grad_rescale_nhw_f32(s.inst.N, s.inst.h, s.inst.w, s.up.ptr(), s.up.ptr() + 4, 2, s.state.ptr(), s.grad.ptr(), st)
+            else:
+                rc = lib.bxi_boxinst_grad_rescale_f32(C.byref(s.inst.struct), s.up.ptr(), s.up.ptr() + 4, 2, s.state.ptr(), s.grad.ptr(), st)
+            assert rc == 0, _lib.status_string(rc)
+            G.check_bands(s.losses, s.grad, s.state, s.ws, *s.inputs())
+            G.check_unchanged(*s.inputs())
+            grad = s.grad.t.cpu().numpy()[:, 0]
+            err, ties = grad_report(grad, ref2['grad'], d['mask_logits'][:, 0])
+            assert np.isfinite(grad).all() and err <= TOL, f'{what}: rescaled grad err {err:.3e}'
+        # the upstream factors read by the evaluation itself, from guarded device scalars
+        if name in ('aligned', 'all'):
+            s = _EvalSet(d, dev, leads, lib, Fh)
+            evaluate(s, (s.up.ptr(), s.up.ptr() + 4))
+            torch.cuda.synchronize()
+            assert s.status() == 0, what
+            G.check_bands(s.losses, s.grad, s.state, s.ws, *s.inputs())
+            G.check_written(s.losses, s.grad)
+            G.check_unchanged(*s.inputs())
+            _assert_eval_result(s, ref2, what + ' upstream (0.5, 3.0)')
+
+
+@pytest.mark.parametrize('canvas', ['w40', 'w41'])
+def test_loss_from_bits_guarded(dev, canvas):
+    """bxi_boxinst_loss_fwd_bwd_f32 (precomputed affinity bits) + bxi_boxinst_loss_backward_f32: mask_loss.hip's `vec` (logits | g_logits)
+    on both sides; workspace and state ("contents undefined") hold the pattern before the call."""
+    from boxinstseg_amd import _lib, color_affinity, functional as Fh
+    lib = _lib.load()
+    d = _canvas(canvas)
+    ref = oracle_path(d, warmup=0.37, g_prj=0.5, g_pw=3.0, want_targets=False)
+    st = _stream(dev)
+    _, bits0, _ = color_affinity(torch.from_numpy(d['imgs']).to(dev), d['img_metas'], want_similarity=False)
+    results = {}
+    for name, leads in {'aligned': {}, 'logits': dict(logits=1), 'g_logits': dict(g_logits=3), 'bits': dict(bits=5), 'gt_inds': dict(gt_inds=1),
+                        'losses': dict(losses=1), 'boxes': dict(boxes=1), 'all': dict(logits=2, g_logits=1, bits=3, gt_inds=1, losses=3, boxes=2, up=1)}.items():
+        s = _EvalSet(d, dev, leads, lib, Fh)
+        bits = G.embed(bits0, leads.get('bits', 0), G.plane_band(d['h'], d['w'], 4))
+        ws = G.out(max(lib.bxi_boxinst_loss_workspace_bytes(s.inst.N, s.inst.h, s.inst.w), 256), torch.uint8, dev, 0, 1024)
+        rc = lib.bxi_boxinst_loss_fwd_bwd_f32(C.byref(s.inst.struct), bits.ptr(), 3, 2, 0.37, s.losses.ptr(), s.grad.ptr(), s.state.ptr(), ws.ptr(),
+                                              ws.numel, st)
+        assert rc == 0, _lib.status_string(rc)
+        G.check_bands(s.losses, s.grad, s.state, ws, bits, *s.inputs())
+        G.check_written(s.losses, s.grad)               # "every element is written exactly once here"
+        rc = lib.bxi_boxinst_loss_backward_f32(C.byref(s.inst.struct), s.up.ptr(), s.up.ptr() + 4, 2, s.state.ptr(), s.grad.ptr(), st)
+        assert rc == 0, _lib.status_string(rc)
+        G.check_bands(s.losses, s.grad, s.state, ws, bits, *s.inputs())
+        G.check_unchanged(bits, *s.inputs())
+        got = s.losses.t.cpu().numpy()
+        # (the forward's losses carry no upstream factor: those of the unit oracle)
+        assert rel(float(got[0]), ref['loss_prj']) <= TOL and rel(float(got[1]), ref['loss_pairwise']) <= TOL, (name, got)
+        grad = s.grad.t.cpu().numpy()[:, 0]
+        err, ties = grad_report(grad, ref['grad'], d['mask_logits'][:, 0])
+        assert np.isfinite(grad).all() and err <= TOL, f'{canvas} {name}: grad err {err:.3e}'
+        results[name] = (got.copy(), grad.copy())
+    # plain fresh tensors, lead 0: bit-identical
+    from tests.helpers import to_dev
+    t = to_dev(d, dev)
+    pi = Fh._Inst(t['logits'], t['gt_inds'], t['gt_bboxes'], d['H'], d['W'], d['stride'])
+    losses, grad = torch.zeros(2, device=dev), torch.empty_like(t['logits'])
+    state = torch.empty(lib.bxi_boxinst_loss_state_bytes(pi.N, pi.h, pi.w), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(lib.bxi_boxinst_loss_workspace_bytes(pi.N, pi.h, pi.w), 256), dtype=torch.uint8, device=dev)
+    up = torch.tensor([0.5, 3.0], device=dev)
+    assert lib.bxi_boxinst_loss_fwd_bwd_f32(C.byref(pi.struct), bits0.data_ptr(), 3, 2, 0.37, losses.data_ptr(), grad.data_ptr(), state.data_ptr(),
+                                            ws.data_ptr(), ws.numel(), st) == 0
+    assert lib.bxi_boxinst_loss_backward_f32(C.byref(pi.struct), up.data_ptr(), up.data_ptr() + 4, 2, state.data_ptr(), grad.data_ptr(), st) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(results['aligned'][0].view(np.int32), losses.cpu().numpy().view(np.int32))
+    assert np.array_equal(results['aligned'][1].view(np.int32), grad.cpu().numpy()[:, 0].view(np.int32))
+
+
+@pytest.mark.parametrize('canvas', ['w40', 'w41', 'stride8'])
+def test_color_affinity_guarded(dev, canvas):
+    """bxi_color_affinity_f32: `imgs` at every 4-byte misalignment (pool_vec_ok's other side with Wc % 4 == 0), lab / sim / bits outputs
+    misaligned; against the C oracle under the rules of test_color_affinity."""
+    from boxinstseg_amd import _lib, functional as Fh
+    lib = _lib.load()
+    if canvas == 'stride8':
+        d = synthetic.make_batch(B=1, H=128, W=192, boxes_per_img=1, seed=5, stride=8, min_box=16, max_box=64)
+    else:
+        d = _canvas(canvas)
+    stride = d['stride']
+    ref = oracle_path(d)
+    B, h, w = d['B'], d['h'], d['w']
+    band = G.plane_band(h, w, 4)
+    imgs0 = torch.from_numpy(d['imgs']).to(dev)
+    plain = None
+    for li, ll, ls, lb in [(0, 0, 0, 0), (1, 0, 0, 0), (2, 0, 0, 0), (3, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 5), (1, 2, 3, 7)]:
+        gi = G.embed(imgs0, li, G.plane_band(d['H'], d['W'], 0))
+        batch = Fh._Batch(gi.t, d['img_metas'], 10)
+        assert batch.imgs.data_ptr() == gi.ptr()
+        lab, sim = G.out((B, 3, h, w), torch.float32, dev, ll, band), G.out((B, 8, h, w), torch.float32, dev, ls, band)
+        bits = G.out((B, h, w), torch.uint8, dev, lb, band)
+        with _Hook() as hk:
+            rc = lib.bxi_color_affinity_f32(C.byref(batch.struct), stride, 3, 2, 0.3, lab.ptr(), None, sim.ptr(), bits.ptr(), _stream(dev))
+        assert rc == 0, _lib.status_string(rc)
+        assert set(hk.names) == {'pool_rgb', 'affinity'}, hk.names
+        G.check_bands(gi, lab, sim, bits)
+        G.check_written(lab, sim)
+        G.check_unchanged(gi)
+        s, b = sim.t.cpu().numpy(), bits.t.cpu().numpy()
+        assert np.abs(s - ref['sim']).max() <= 2e-6
+        ambiguous = 0
+        for k in range(8):
+            mism = (((b >> k) & 1) != (ref['sim'][:, k] >= 0.3)).astype(bool)
+            near = np.abs(ref['sim'][:, k] - 0.3) <= 4e-6
+            assert not (mism & ~near).any(), f'direction {k}: {(mism & ~near).sum()} threshold flips away from the threshold'
+            ambiguous += int((mism & near).sum())
+        assert ambiguous <= 2
+        if plain is None:
+            from boxinstseg_amd import color_affinity
+            psim, pbits, plab = color_affinity(imgs0, d['img_metas'], out_stride=stride)
+            assert torch.equal(psim.view(torch.int32), sim.t.view(torch.int32)) and torch.equal(pbits, bits.t)
+            assert torch.equal(plab.view(torch.int32), lab.t.view(torch.int32))
+            plain = True
+
+
+def test_box_bitmasks_guarded(dev):
+    """bxi_box_bitmasks_f32: the box arrays as slices of one misaligned tensor (an image without boxes among them), the output misaligned."""
+    from boxinstseg_amd import _lib
+    from oracle import c_oracle
+    lib = _lib.load()
+    boxes = [np.array([[10.7, 3.2, 50.9, 40.1], [-3.0, -2.0, 20.0, 10.0], [60.0, 60.0, 200.0, 200.0], [5.0, 5.0, 5.9, 5.9], [30.0, 2.0, 10.0, 60.0]], np.float32),
+             np.zeros((0, 4), np.float32), np.array([[0.0, 0.0, 95.0, 63.0]], np.float32)]
+    allb = np.concatenate(boxes)
+    H, W = 64, 96
+    cnt = _lib.int_array(len(b) for b in boxes)
+    for stride, start in ((4, 2), (1, 0)):
+        h, w = (H - start + stride - 1) // stride, (W - start + stride - 1) // stride
+        for lb, lo in [(0, 0), (1, 0), (3, 0), (0, 1), (2, 3)]:
+            gb = G.embed(torch.from_numpy(allb).to(dev), lb, 64)
+            views = [gb.t[0:5], gb.t[5:5], gb.t[5:6]]
+            ptrs = _lib.ptr_array(v.data_ptr() if v.numel() else 0 for v in views)
+            go = G.out((len(allb), h, w), torch.float32, dev, lo, G.plane_band(h, w, 0))
+            rc = lib.bxi_box_bitmasks_f32(C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(cnt, C.POINTER(C.c_int)), 3, H, W, stride, start, go.ptr(), _stream(dev))
+            assert rc == 0, _lib.status_string(rc)
+            G.check_bands(gb, go)
+            G.check_written(go)
+            G.check_unchanged(gb)
+            got = go.t.cpu().numpy()
+            for g, box in enumerate(allb):
+                full = np.zeros((H, W), np.float32)
+                full[int(box[1]):int(box[3]) + 1, int(box[0]):int(box[2]) + 1] = 1.0
+                assert np.array_equal(got[g], full[start::stride, start::stride]), (g, stride, lb, lo)
+                if stride == 4:
+                    assert np.array_equal(got[g], c_oracle.box_bitmask(box, H, W, 4))
+
+
+# ---------------------------------------------------------------------------------------------
+# test-time mask paste
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('out_w', [64, 61], ids=['out_w_64', 'out_w_61'])
+def test_mask_paste_guarded(dev, out_w):
+    """bxi_mask_paste_u8: `masks` at every byte offset 0..15 with an out_w that is (64) and one that is not (61) a multiple of 16 --
+    mask_paste.hip's per-item predicate (16 bytes and a 16-byte aligned destination) takes both sides within one call as the rows move --,
+    `logits` at lead 1-3, out_offsets / img_inds at lead 1.  The tie rule of test_gpu_mask_paste.py against the fp64 composition."""
+    from boxinstseg_amd import _lib
+    from tests.test_gpu_mask_paste import check_tie
+    lib = _lib.load()
+    rng = np.random.default_rng(77)
+    h, w, factor = 12, 18, 4
+    dims = [(48, 72, 30, out_w), (41, 70, 41, out_w)]
+    img = np.array([0, 1, 1, 0, 1], np.int64)
+    logits0 = torch.from_numpy((rng.standard_normal((len(img), 1, h, w)) * 3).astype(np.float32)).to(dev)
+    sizes = [dims[i][2] * dims[i][3] for i in img]
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    total = int(np.sum(sizes))
+    flat = [int(v) for dd in dims for v in dd]
+    dims_host = (C.c_int32 * len(flat))(*flat)
+    plain = torch.empty(total, dtype=torch.uint8, device=dev)
+    img_t, off_t = torch.from_numpy(img).to(dev), torch.from_numpy(offs).to(dev)
+    assert lib.bxi_mask_paste_u8(logits0.data_ptr(), len(img), h, w, factor, img_t.data_ptr(), off_t.data_ptr(), 2, dims_host, 0.5, plain.data_ptr(),
+                                 _stream(dev)) == 0
+    cases = [(0, lm, 0) for lm in range(16)] + [(1, 0, 0), (2, 5, 0), (3, 0, 0), (0, 0, 1), (3, 9, 1)]
+    for ll, lm, li in cases:
+        gl = G.embed(logits0, ll, G.plane_band(h, w, 0))
+        gi, gofs = G.embed(img_t, li, 64), G.embed(off_t, li, 64)
+        gm = G.out(total, torch.uint8, dev, lm, 1024)
+        rc = lib.bxi_mask_paste_u8(gl.ptr(), len(img), h, w, factor, gi.ptr(), gofs.ptr(), 2, dims_host, 0.5, gm.ptr(), _stream(dev))
+        assert rc == 0, _lib.status_string(rc)
+        G.check_bands(gl, gi, gofs, gm)
+        G.check_written(gm)
+        G.check_unchanged(gl, gi, gofs)
+        got = gm.t.cpu().numpy()
+        for j in range(len(img)):
+            dd = dims[img[j]]
+            check_tie(got[offs[j]:offs[j] + sizes[j]].reshape(1, dd[2], dd[3]), logits0[j:j + 1], factor, dd, f'instance {j} lead {(ll, lm, li)}')
+        # the same arithmetic whatever the alignment of the destination: bit-identical to the plain call
+        assert torch.equal(gm.t, plain), (ll, lm, li)
+
+
+# ---------------------------------------------------------------------------------------------
+# LevelsetLoss at the ABI: outputs and state inside bands as well
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('N,H,W,Cc', [(3, 12, 20, 3), (2, 9, 7, 2), (2, 24, 40, 9), (2, 31, 33, 16)])
+def test_levelset_guarded(dev, N, H, W, Cc):
+    """bxi_levelset_loss_forward_f32 / _backward_f32 with inputs, outputs and state guarded: levelset.hip's `vec` (H * W % 4 == 0 and
+    mask_score | target 16-byte aligned) with mask_score and target misaligned SEPARATELY at plane sizes that allow the vector kernel
+    (12 x 20, 24 x 40) next to sizes that never do; the last instance's planes end at the band, so a reduction that reads past a plane
+    meets NaN and a store past g_mask_score / g_target meets the pattern.  Against the numpy oracle at 1e-4 (test_gpu_levelset.py)."""
+    from boxinstseg_amd import _lib
+    from oracle import levelset_oracle as lo
+    from tests.test_gpu_levelset import _close
+    lib = _lib.load()
+    rng = np.random.default_rng(N * 100 + W)
+    box = np.zeros((N, 1, H, W), np.float32)
+    for i in range(N):
+        r0, c0 = int(rng.integers(0, max(H // 2, 1))), int(rng.integers(0, max(W // 2, 1)))
+        box[i, 0, r0:r0 + int(rng.integers(1, H // 2 + 2)), c0:c0 + int(rng.integers(1, W // 2 + 2))] = rng.uniform(0.3, 1.0)
+    ms = (rng.uniform(0, 1, (N, 2, H, W)) * (box > 0)).astype(np.float32)
+    T = rng.uniform(-1, 1, (N, Cc, H, W)).astype(np.float32)
+    pn = np.maximum((box > 0).sum((1, 2, 3)), 1).astype(np.float32)
+    gl = rng.uniform(0.5, 2.0, size=N).astype(np.float32)
+    lw, gm, gT = lo.levelset_loss(ms, T, pn, 5.0)
+    g4 = gl[:, None, None, None]
+    band = G.plane_band(H, W)
+    st = _stream(dev)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    state_bytes = max(lib.bxi_levelset_state_bytes(N, Cc), 16)
+    plain = None
+    for name, L in {'aligned': {}, 'mask_score': dict(ms=1), 'target': dict(T=1), 'g_mask_score': dict(gms=2), 'g_target': dict(gT=3),
+                    'all': dict(ms=3, T=2, pn=1, gl=3, loss=1, gms=1, gT=2)}.items():
+        gms_in, gT_in, gpn, ggl = G.embed(t(ms), L.get('ms', 0), band), G.embed(t(T), L.get('T', 0), band), G.embed(t(pn), L.get('pn', 0), 64), \
+            G.embed(t(gl), L.get('gl', 0), 64)
+        loss, state = G.out(N, torch.float32, dev, L.get('loss', 0), 64), G.out(state_bytes, torch.uint8, dev, 0, 1024)
+        o_ms, o_T = G.out((N, 2, H, W), torch.float32, dev, L.get('gms', 0), band), G.out((N, Cc, H, W), torch.float32, dev, L.get('gT', 0), band)
+        ins, outs = [gms_in, gT_in, gpn, ggl], [loss, state, o_ms, o_T]
+        with _Hook() as hk:
+            rc = lib.bxi_levelset_loss_forward_f32(gms_in.ptr(), gT_in.ptr(), gpn.ptr(), N, Cc, H, W, 5.0, loss.ptr(), state.ptr(), st)
+            assert rc == 0, _lib.status_string(rc)
+            G.check_bands(*ins, *outs)
+            G.check_written(loss)
+            rc = lib.bxi_levelset_loss_backward_f32(gms_in.ptr(), gT_in.ptr(), gpn.ptr(), N, Cc, H, W, 5.0, state.ptr(), ggl.ptr(), o_ms.ptr(),
+                                                    o_T.ptr(), st)
+            assert rc == 0, _lib.status_string(rc)
+        assert {'levelset_partial', 'levelset_finish', 'levelset_bwd'} <= set(hk.names), hk.names
+        G.check_bands(*ins, *outs)
+        G.check_written(loss, o_ms, o_T)
+        G.check_unchanged(*ins)
+        assert _close(loss.t.cpu().numpy(), lw), name
+        assert _close(o_ms.t.cpu().numpy(), gm * g4) and _close(o_T.t.cpu().numpy(), gT * g4), name
+        if name == 'aligned':
+            p_loss, p_state = torch.empty(N, device=dev), torch.empty(state_bytes, dtype=torch.uint8, device=dev)
+            p_ms, p_T, x_ms, x_T, x_pn, x_gl = torch.empty_like(o_ms.t), torch.empty_like(o_T.t), t(ms), t(T), t(pn), t(gl)
+            assert lib.bxi_levelset_loss_forward_f32(x_ms.data_ptr(), x_T.data_ptr(), x_pn.data_ptr(), N, Cc, H, W, 5.0, p_loss.data_ptr(),
+                                                     p_state.data_ptr(), st) == 0
+            assert lib.bxi_levelset_loss_backward_f32(x_ms.data_ptr(), x_T.data_ptr(), x_pn.data_ptr(), N, Cc, H, W, 5.0, p_state.data_ptr(),
+                                                      x_gl.data_ptr(), p_ms.data_ptr(), p_T.data_ptr(), st) == 0
+            torch.cuda.synchronize()
+            i32 = torch.int32
+            assert torch.equal(p_loss.view(i32), loss.t.view(i32)) and torch.equal(p_ms.view(i32), o_ms.t.view(i32)) and torch.equal(p_T.view(i32), o_T.t.view(i32))
