@@ -163,6 +163,23 @@ __device__ __forceinline__ float wave_max_f32(float v) {
     return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 0)), __int_as_float(__builtin_amdgcn_readlane(b, 16))),
                  fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 32)), __int_as_float(__builtin_amdgcn_readlane(b, 48))));
 }
+__device__ __forceinline__ int wave_min_i32(int v) {
+    wave_total_steps([&](int c) { v = min(v, dpp_i32(v, c)); });
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+// The column a row's arg-max goes to, from per-lane (maximum, its first column) pairs and the wave's maximum: the SMALLEST column among
+// the lanes that hold the maximum.  A lane owns four columns of every 256-column chunk, so with one chunk the lowest such lane holds it
+// (one ballot + readlane); with several chunks a low lane may hold a column of a later chunk (column 256 is lane 0, column 255 lane 63),
+// and the columns themselves are compared.  No lane holds the maximum only for a row of NaN: column 0 then, as before.
+__device__ __forceinline__ int first_col_of_max(float lane_max, int lane_col, float wave_max, bool one_chunk) {
+    const bool mine = lane_max == wave_max;
+    if (one_chunk) {
+        const unsigned long long who = __ballot(mine);
+        return __builtin_amdgcn_readlane(lane_col, who ? __ffsll((long long)who) - 1 : 0);
+    }
+    const int col = wave_min_i32(mine ? lane_col : 0x7fffffff);
+    return col == 0x7fffffff ? __builtin_amdgcn_readlane(lane_col, 0) : col;
+}
 // (the historical names: every kernel's wave reduction goes through the DPP forms above)
 __device__ __forceinline__ float wave_sum_f32(float v) { return wave_total_f32(v); }
 __device__ __forceinline__ double wave_sum_f64(double v) { return wave_total_f64(v); }

@@ -577,9 +577,7 @@ __device__ __forceinline__ void stream_block(const InstArgs& a, Ws& ws, float* _
     unsigned long long mine = 0ull;
 #pragma unroll
     for (int i = 0; i < kSRows; ++i) {
-        const unsigned long long who = __ballot(rmax[i] == wmax[i]);
-        const int first = who ? __ffsll((long long)who) - 1 : 0;
-        const int col = __builtin_amdgcn_readlane(rcol[i], first);
+        const int col = first_col_of_max(rmax[i], rcol[i], wmax[i], w <= kChunkC);
         if (lane == i) mine = pack_max(wmax[i], (uint32_t)col);
     }
     if (lane < kSRows && r0 + lane < r1) {

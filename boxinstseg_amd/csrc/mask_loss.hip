@@ -224,8 +224,8 @@ __device__ __forceinline__ void stream_tile(const InstArgs& a, int dil, const Lo
     }
     BXI_T(0, blockIdx.x, 4);
     // row maxima: kSR independent 32-bit butterflies advanced in lock step (their cross-lane moves
-    // pipeline); the arg-max is the lowest lane holding the maximum (lanes own ascending columns),
-    // found with one ballot + readlane per row.
+    // pipeline); the arg-max is the smallest column among the lanes holding the maximum (first_col_of_max:
+    // within one chunk the lowest such lane, one ballot + readlane per row).
     float wmax[kSR];
 #pragma unroll
     for (int i = 0; i < kSR; ++i) wmax[i] = rmax[i];
@@ -240,9 +240,7 @@ __device__ __forceinline__ void stream_tile(const InstArgs& a, int dil, const Lo
     unsigned long long mine = 0ull;
 #pragma unroll
     for (int i = 0; i < kSR; ++i) {
-        const unsigned long long who = __ballot(rmax[i] == wmax[i]);
-        const int first = who ? __ffsll((long long)who) - 1 : 0;
-        const int col = __builtin_amdgcn_readlane(rcol[i], first);
+        const int col = first_col_of_max(rmax[i], rcol[i], wmax[i], w <= kChunk);
         if (lane == i) mine = pack_max(wmax[i], (uint32_t)col);
     }
     if (lane < kSR && r0 + lane < r1) ws.rowkey[(int64_t)n * h + r0 + lane] = mine;

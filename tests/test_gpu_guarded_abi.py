@@ -17,7 +17,7 @@ import torch
 
 from boxinstseg_amd import synthetic
 from tests import guarded as G
-from tests.helpers import grad_report, oracle_path, rel
+from tests.helpers import expected_grad_logit_first, grad_check_all_lines, grad_report, oracle_path, rel
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -215,7 +215,7 @@ class _EvalSet:
         return int(self.state.t[self.status_off:self.status_off + 4].view(torch.int32).item())
 
 
-def _assert_eval_result(s, ref, what):
+def _assert_eval_result(s, ref, what, g_prj=1.0):
     got = s.losses.t.cpu().numpy()
     assert np.isfinite(got).all(), (what, got)
     assert rel(float(got[0]), ref['loss_prj']) <= TOL, (what, got, ref['loss_prj'])
@@ -224,6 +224,9 @@ def _assert_eval_result(s, ref, what):
     assert np.isfinite(grad).all(), what
     err, ties = grad_report(grad, ref['grad'], s.d['mask_logits'][:, 0])
     assert err <= TOL, f'{what}: grad err {err:.3e} ({ties} ambiguous arg-max lines excluded)'
+    # and the excluded lines too: every pixel against the first index of the largest logit (tests/helpers.py:expected_grad_logit_first)
+    err = grad_check_all_lines(grad, expected_grad_logit_first(s.d, ref, g_prj))
+    assert err <= TOL, f'{what}: grad err {err:.3e} over every line'
 
 
 EVAL_FORMS = ['default', 'single_launch', 'single_launch_shared_device', 'two_launches_4_row_tiles', 'two_launches_8_row_tiles', 'targets_ahead']
@@ -307,7 +310,7 @@ def test_eval_guarded(dev, canvas, form):
             G.check_bands(s.losses, s.grad, s.state, s.ws, *s.inputs())
             G.check_written(s.losses, s.grad)
             G.check_unchanged(*s.inputs())
-            _assert_eval_result(s, ref2, what + ' upstream (0.5, 3.0)')
+            _assert_eval_result(s, ref2, what + ' upstream (0.5, 3.0)', g_prj=0.5)
 
 
 @pytest.mark.parametrize('canvas', ['w40', 'w41'])

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from boxinstseg_amd import synthetic
-from tests.helpers import grad_report, hip_loss, oracle_path, rel, to_dev
+from tests.helpers import expected_grad_logit_first, grad_check_all_lines, grad_report, hip_loss, oracle_path, rel, to_dev
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -278,7 +278,15 @@ def _check(d, dev, warmup=1.0, up=None, tol=TOL):
     assert err <= tol, f'grad err {err:.3e} ({ties} ambiguous arg-max lines excluded)'
     raw = float(np.abs(grad - ref['grad']).max() / np.abs(ref['grad']).max())
     assert raw <= tol or ties > 0, f'raw grad err {raw:.3e} with no ambiguous arg-max line'
+    _check_all_lines(d, ref, grad, g[0], tol)
     return lp, lw
+
+
+def _check_all_lines(d, ref, grad, g_prj=1.0, tol=TOL):
+    """What grad_report leaves out is checked as well: every pixel against the oracle's gradient with each line's projection mass at the
+    first index of the largest logit (tests/helpers.py:expected_grad_logit_first), no line excluded."""
+    err = grad_check_all_lines(grad, expected_grad_logit_first(d, ref, g_prj))
+    assert err <= tol, f'grad err {err:.3e} over every line, against the first index of the largest logit'
 
 
 def test_loss_cfg1(dev):
@@ -312,6 +320,7 @@ def test_loss_extreme_logits(dev):
     lp, lw, grad = hip_loss(d, dev)
     assert np.isfinite([lp, lw]).all() and np.isfinite(grad).all()
     assert rel(lw, ref['loss_pairwise']) <= TOL and rel(lp, ref['loss_prj']) <= TOL
+    _check_all_lines(d, ref, grad)          # (511 of its 512 lines have tied fp32 sigmoids: grad_report would compare one line)
 
 
 def test_loss_zero_instances_and_empty_image(dev):
@@ -794,6 +803,7 @@ def _check_cfg(d, dev, tol=TOL, **kw):
     assert rel(lw, ref['loss_pairwise']) <= tol or abs(lw - ref['loss_pairwise']) < 1e-7, (lw, ref['loss_pairwise'])
     err, ties = grad_report(grad, ref['grad'], d['mask_logits'][:, 0])
     assert err <= tol, f'grad err {err:.3e} ({ties} ambiguous arg-max lines excluded)'
+    _check_all_lines(d, ref, grad, 1.0, tol)
 
 
 def test_loss_many_instances(dev):
@@ -957,6 +967,7 @@ def test_loss_fuzz(dev, seed):
     assert rel(lw, ref['loss_pairwise']) <= TOL or abs(lw - ref['loss_pairwise']) < 1e-7, (lw, ref['loss_pairwise'])
     err, ties = grad_report(grad, ref['grad'], d['mask_logits'][:, 0])
     assert err <= TOL, f'grad err {err:.3e} ({ties} ambiguous arg-max lines excluded); cfg {B}x{H}x{W} s{stride} {kw}'
+    _check_all_lines(d, ref, grad, up[0])
 
 
 def test_many_shapes_in_one_process_without_resets(dev):
