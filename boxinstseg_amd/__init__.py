@@ -10,6 +10,8 @@ Public surface (mirrors the reference's for this path):
     MeanField, dice_loss, mil_loss     <-> mmdet.models.dense_heads.discobox_head
     BoxProjectionLoss, LevelsetLoss, LocalConsistencyModule, LCM <-> mmdet.models.losses
     MinimumSpanningTree, TreeFilter2D, mst, bfs, refine <-> mmdet.ops.tree_filter
+    mask_matrix_nms                    <-> mmdet.core.post_processing.mask_matrix_nms
+    seg_nms, box_solov2_get_seg_single, discobox_get_seg_single : the test-time block of the SOLOv2-style heads (get_seg_single)
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -19,6 +21,7 @@ from .discobox import MeanField, dice_loss, meanfield_forward, meanfield_kernel,
 from .levelset import LCM, BoxProjectionLoss, LevelsetLoss, LocalConsistencyModule, region_levelset
 from .registry import HEADS, LOSSES, build_head, build_loss
 from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
+from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask_matrix_nms, seg_nms
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -26,5 +29,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'CondInstMaskHead', 'HEADS', 'build_head', 'load_config',
            'MeanField', 'meanfield_kernel', 'meanfield_forward', 'dice_loss', 'mil_loss',
            'BoxProjectionLoss', 'LevelsetLoss', 'region_levelset', 'LocalConsistencyModule', 'LCM', 'LOSSES', 'build_loss',
-           'MinimumSpanningTree', 'TreeFilter2D', 'mst', 'bfs', 'refine']
+           'MinimumSpanningTree', 'TreeFilter2D', 'mst', 'bfs', 'refine',
+           'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single']
 __version__ = '0.1.0'

@@ -132,6 +132,17 @@ SIGNATURES = {
                                                     c_void_p, c_size_t, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_post.h (test-time post-processing of the SOLOv2-style heads); applied by load() next to SIGNATURES
+NMS_KERNELS = {'gaussian': 0, 'linear': 1}
+NMS_MAX_CANDIDATES = 2048
+POST_SIGNATURES = {
+    'bxi_mask_pack_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bxi_mask_pack_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'bxi_matrix_nms_workspace_bytes': (c_size_t, [c_int]),
+    'bxi_matrix_nms_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -152,7 +163,7 @@ def load() -> C.CDLL:
                 '(run `python -c "import __graft_entry__ as g; g.build()"` or `python -m boxinstseg_amd.build`). '
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
