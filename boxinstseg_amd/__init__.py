@@ -12,6 +12,8 @@ Public surface (mirrors the reference's for this path):
     MinimumSpanningTree, TreeFilter2D, mst, bfs, refine <-> mmdet.ops.tree_filter
     mask_matrix_nms                    <-> mmdet.core.post_processing.mask_matrix_nms
     seg_nms, box_solov2_get_seg_single, discobox_get_seg_single : the test-time block of the SOLOv2-style heads (get_seg_single)
+    ClassificationCost, BoxMatchingCost, MaskHungarianAssigner <-> mmdet.core.bbox match costs / assigner of Box2Mask
+    box2mask_get_targets               <-> Box2MaskHead.get_targets (matching cost and Hungarian assignment of a whole batch)
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -19,9 +21,10 @@ from .dynamic import DynamicMaskHead, dynamic_mask_forward, paste_masks, paste_m
 from .mask_head import CondInstMaskHead
 from .discobox import MeanField, dice_loss, meanfield_forward, meanfield_kernel, mil_loss
 from .levelset import LCM, BoxProjectionLoss, LevelsetLoss, LocalConsistencyModule, region_levelset
-from .registry import HEADS, LOSSES, build_head, build_loss
+from .registry import BBOX_ASSIGNERS, HEADS, LOSSES, MATCH_COST, build_assigner, build_head, build_loss, build_match_cost
 from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
 from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask_matrix_nms, seg_nms
+from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigner, box2mask_get_targets
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -30,5 +33,7 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'MeanField', 'meanfield_kernel', 'meanfield_forward', 'dice_loss', 'mil_loss',
            'BoxProjectionLoss', 'LevelsetLoss', 'region_levelset', 'LocalConsistencyModule', 'LCM', 'LOSSES', 'build_loss',
            'MinimumSpanningTree', 'TreeFilter2D', 'mst', 'bfs', 'refine',
-           'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single']
+           'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single',
+           'ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'box2mask_get_targets', 'MATCH_COST', 'BBOX_ASSIGNERS',
+           'build_match_cost', 'build_assigner']
 __version__ = '0.1.0'

@@ -86,6 +86,28 @@ def _make_losses():
 LOSSES = _make_losses()      # BoxProjectionLoss, LevelsetLoss (mmdet/models/builder.py: LOSSES)
 
 
+def _make_match_costs():
+    try:
+        from mmdet.core.bbox.match_costs.builder import MATCH_COST as mm_costs
+        return _MMDetHeads(mm_costs)
+    except Exception:
+        return Registry('Match Cost')
+
+
+MATCH_COST = _make_match_costs()      # ClassificationCost, BoxMatchingCost (mmdet/core/bbox/match_costs/builder.py: MATCH_COST)
+
+
+def _make_assigners():
+    try:
+        from mmdet.core.bbox.builder import BBOX_ASSIGNERS as mm_assigners
+        return _MMDetHeads(mm_assigners)
+    except Exception:
+        return Registry('bbox_assigner')
+
+
+BBOX_ASSIGNERS = _make_assigners()    # MaskHungarianAssigner (mmdet/core/bbox/builder.py: BBOX_ASSIGNERS)
+
+
 def build_head(cfg: dict, default_args: Optional[dict] = None):
     """``mmdet.models.builder.build_head`` for the heads this package provides."""
     return HEADS.build(cfg, default_args=default_args)
@@ -94,3 +116,13 @@ def build_head(cfg: dict, default_args: Optional[dict] = None):
 def build_loss(cfg: dict, default_args: Optional[dict] = None):
     """``mmdet.models.builder.build_loss`` for the losses this package provides."""
     return LOSSES.build(cfg, default_args=default_args)
+
+
+def build_match_cost(cfg: dict, default_args: Optional[dict] = None):
+    """``mmdet.core.bbox.match_costs.build_match_cost`` for the matching costs this package provides."""
+    return MATCH_COST.build(cfg, default_args=default_args)
+
+
+def build_assigner(cfg: dict, default_args: Optional[dict] = None):
+    """``mmdet.core.bbox.build_assigner`` for the assigners this package provides."""
+    return BBOX_ASSIGNERS.build(cfg, default_args=default_args)
