@@ -14,6 +14,9 @@ Public surface (mirrors the reference's for this path):
     seg_nms, box_solov2_get_seg_single, discobox_get_seg_single : the test-time block of the SOLOv2-style heads (get_seg_single)
     ClassificationCost, BoxMatchingCost, MaskHungarianAssigner <-> mmdet.core.bbox match costs / assigner of Box2Mask
     box2mask_get_targets               <-> Box2MaskHead.get_targets (matching cost and Hungarian assignment of a whole batch)
+    nms, batched_nms                   <-> mmcv.ops.nms.nms / batched_nms (greedy box NMS, one workgroup per image)
+    nms_with_others                    <-> mmdet.models.dense_heads.condinst_head.nms_with_others
+    condinst_get_bboxes                <-> CondInstBoxHead.get_bboxes (decode, score filter and box NMS of a whole batch, one sync)
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -25,6 +28,7 @@ from .registry import BBOX_ASSIGNERS, HEADS, LOSSES, MATCH_COST, build_assigner,
 from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
 from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask_matrix_nms, seg_nms
 from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigner, box2mask_get_targets
+from .box_nms import batched_nms, condinst_get_bboxes, nms, nms_with_others
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -35,5 +39,5 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'MinimumSpanningTree', 'TreeFilter2D', 'mst', 'bfs', 'refine',
            'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single',
            'ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'box2mask_get_targets', 'MATCH_COST', 'BBOX_ASSIGNERS',
-           'build_match_cost', 'build_assigner']
+           'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes']
 __version__ = '0.1.0'

@@ -158,6 +158,28 @@ ASSIGN_SIGNATURES = {
                                               c_void_p, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_det.h (CondInst test-time detections: decode, score filter, box NMS); applied by load() as well
+DET_MAX_LEVELS, DET_SORT_MAX, DET_NMS_ROUND, DET_KEEP_TILE, DET_ROW_TILE = 8, 16384, 256, 2048, 64
+DET_STATUS_OVER_CAP, DET_STATUS_OVER_SORT, DET_STATUS_BAD_ORDER = 1, 2, 4
+
+
+class DetLevel(C.Structure):
+    """struct bxi_det_level"""
+    _fields_ = [('cls', c_void_p), ('bbox', c_void_p), ('ctr', c_void_p), ('params', c_void_p), ('H', c_int), ('W', c_int), ('stride', c_int)]
+
+
+DET_SIGNATURES = {
+    'bxi_det_location_score_f32': (c_int, [C.POINTER(DetLevel), c_int, c_int, c_int, c_void_p, c_void_p]),
+    'bxi_det_candidates_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'bxi_det_candidates_f32': (c_int, [C.POINTER(DetLevel), c_int, c_int, c_int, c_void_p, c_int, C.POINTER(c_float), c_int, c_float, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_box_nms_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_box_nms_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_det_gather_f32': (c_int, [C.POINTER(DetLevel), c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -178,7 +200,8 @@ def load() -> C.CDLL:
                 '(run `python -c "import __graft_entry__ as g; g.build()"` or `python -m boxinstseg_amd.build`). '
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + \
+                list(DET_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -209,6 +232,11 @@ def check(fn: str, status: int) -> None:
 def int_array(values) -> C.Array:
     values = [int(v) for v in values]
     return (c_int * max(len(values), 1))(*values)
+
+
+def float_array(values) -> C.Array:
+    values = [float(v) for v in values]
+    return (c_float * max(len(values), 1))(*values)
 
 
 def ptr_array(values) -> C.Array:
