@@ -17,6 +17,9 @@ Public surface (mirrors the reference's for this path):
     nms, batched_nms                   <-> mmcv.ops.nms.nms / batched_nms (greedy box NMS, one workgroup per image)
     nms_with_others                    <-> mmdet.models.dense_heads.condinst_head.nms_with_others
     condinst_get_bboxes                <-> CondInstBoxHead.get_bboxes (decode, score filter and box NMS of a whole batch, one sync)
+    condinst_box_targets               <-> CondInstBoxHead.get_targets / centerness_target (FCOS assignment of a whole batch, one launch)
+    condinst_box_loss                  <-> CondInstBoxHead.loss (focal, IoU / GIoU and centerness loss with gradients, no sync)
+    parse_box_head_cfg                 : the bbox_head block of the reference's configs as condinst_box_loss takes it
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -29,6 +32,7 @@ from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
 from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask_matrix_nms, seg_nms
 from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigner, box2mask_get_targets
 from .box_nms import batched_nms, condinst_get_bboxes, nms, nms_with_others
+from .box_head_loss import condinst_box_loss, condinst_box_targets, parse_box_head_cfg
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -39,5 +43,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'MinimumSpanningTree', 'TreeFilter2D', 'mst', 'bfs', 'refine',
            'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single',
            'ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'box2mask_get_targets', 'MATCH_COST', 'BBOX_ASSIGNERS',
-           'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes']
+           'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes',
+           'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg']
 __version__ = '0.1.0'

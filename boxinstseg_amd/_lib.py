@@ -180,6 +180,32 @@ DET_SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_fcos.h (the box head's training step: FCOS targets, focal / IoU / centerness loss); applied by load() as well
+FCOS_GT_CHUNK, FCOS_LOC_TILE, FCOS_ELEM_TILE, FCOS_STATUS_BAD_LABEL = 64, 256, 1024, 1
+FCOS_BBOX_KINDS = {'giou': 0, 'iou_log': 1, 'iou_linear': 2, 'iou_square': 3}
+
+
+class FcosLevel(C.Structure):
+    """struct bxi_fcos_level"""
+    _fields_ = [('H', c_int), ('W', c_int), ('stride', c_int)]
+
+
+class FcosGrads(C.Structure):
+    """struct bxi_fcos_grads"""
+    _fields_ = [('cls', c_void_p), ('bbox', c_void_p), ('ctr', c_void_p)]
+
+
+FCOS_SIGNATURES = {
+    'bxi_fcos_workspace_bytes': (c_size_t, [C.POINTER(FcosLevel), c_int, c_int, c_int]),
+    'bxi_fcos_targets_f32': (c_int, [C.POINTER(FcosLevel), c_int, c_int, C.POINTER(c_float), c_int, C.c_double, c_int, c_int, c_void_p, c_void_p,
+                                     C.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    'bxi_fcos_loss_f32': (c_int, [C.POINTER(DetLevel), c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float,
+                                  c_float, c_float, c_int, c_float, C.POINTER(FcosGrads), c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_fcos_grad_rescale_f32': (c_int, [C.POINTER(FcosLevel), c_int, c_int, c_int, C.POINTER(FcosGrads), c_void_p, C.POINTER(FcosGrads),
+                                          c_void_p]),
+}
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -201,7 +227,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         for name, (res, args) in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + \
-                list(DET_SIGNATURES.items()):
+                list(DET_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -38,6 +38,17 @@ def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
     return rank, world, local_rank
 
 
+def reduce_mean(t: torch.Tensor) -> torch.Tensor:
+    """``mmdet.core.utils.reduce_mean``: the mean of ``t`` over the ranks, as a new tensor; ``t`` itself without a process group of more
+    than one rank (no collective, no copy).  The box head's loss sends its two normalisers through ONE such call
+    (box_head_loss.condinst_box_loss); the reference issues one all-reduce per scalar (condinst_head.py:443, :452-453)."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return t
+    out = t.detach().clone()
+    dist.all_reduce(out.div_(dist.get_world_size()), op=dist.ReduceOp.SUM)
+    return out
+
+
 def _key_digest(keys) -> int:
     """order-sensitive 31-bit digest of the logged key names (same on every rank iff the key lists agree)."""
     import zlib
