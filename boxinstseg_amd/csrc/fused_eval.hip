@@ -23,8 +23,10 @@
 //                   -- each unordered pair ONCE PER IMAGE, not once per instance and tile -- and the segment's share of the pair
 //                   weights' sum (a function of the image and the boxes only, :1324-1328) -> one packed integer atomic per workgroup;
 //                   the reducer (one wave, right behind them in the grid) adds the 64 count words up and publishes ONE word (1 << 63 | sum W)
-//     tile waves    one wave64 per box tile (no LDS, no barrier): logits tile + halo in registers, every unordered pair
-//                   evaluated once; g_pw warm/max(sum W,1) d pw is ADDED (float atomic) to the gradient -- an element receives
+//     tile waves    one wave64 per box tile (no barrier; LDS only to park its own pair terms): logits tile + halo in registers, every unordered pair
+//                   evaluated once -- in the un-split single launch (4-row tiles, dilation 2) the part of a pair that needs the logits alone (log2 S, 1 / S) AHEAD of the
+//                   wait for the predicate words, the weighted sums behind it;
+//                   g_pw warm/max(sum W,1) d pw is ADDED (float atomic) to the gradient -- an element receives
 //                   at most two additions onto 0 (its tile's and its leader's), so the sum does not depend on their order;
 //                   the tile's share of sum W pw goes to an integer accumulator by an atomic without return.  Its two waits:
 //                   its own predicate bytes (bit 7 = evaluated) before the pair loop, the published sum W (the global
@@ -769,6 +771,26 @@ __global__ __launch_bounds__(256) void pack_lab4_kernel(const float* __restrict_
 // ================================================================================================
 template <int D, int R> struct TG { static constexpr int RD = R + 2 * D, TW = 64 - 2 * D; };
 
+// The tile wave's pair terms that need the logits alone (log2 S and 1 / S of every pair) computed AHEAD of its wait for the predicate words and
+// parked -- math_tile, phases A and B.  4-row tiles at dilation 2 only (the 8-row forms have twice the pairs and no room to park them; at
+// dilation 1 the scalar loop, once split, is contracted differently by the compiler and no longer gives the un-split loop's bits: R12-1);
+// one switch per kernel: the single launch that computes the image side (eval1_kernel<D, 4, false>), the single launch with the targets ready
+// (eval1_kernel<D, 4, true>) and the second launch of the two-launch form (pair_kernel<D, 4>).  ON only where tile waves are resident before
+// their words: in the other two every tile wave finds its words at once, phases A and B run back to back in every wave of a CU at the same
+// time, and the parking traffic (16 KB through the LDS per wave) costs more than nothing -- targets ready, single launch: 13.6 -> 13.9 us at
+// 32 instances, 16.85 -> 17.25 at 64; two launches at 64 instances: 22.2 -> 22.35, targets ready 17.4-17.8 -> 18.3 (profiles/NOTES.md R12-1).
+// The terms and their order are the same either way, so every form gives the same bits with a switch on or off.
+enum { kTilesPair = 0, kTilesOne = 1, kTilesOneReady = 2 };
+constexpr bool kAheadOne = true, kAheadOneReady = false, kAheadTwo = false;
+constexpr bool pair_ahead(int D, int R, int kern) {
+    return R == 4 && D == 2 && (kern == kTilesOne ? kAheadOne : kern == kTilesOneReady ? kAheadOneReady : kAheadTwo);
+}
+constexpr int kParkBytes = 8192;                // LDS per tile wave for parked terms (128 bytes per lane); what does not fit stays in registers
+// LDS of ONE tile wave: the log-space path's [R + 1][64] floats (slow_tile) and the parked pair terms share it -- a tile takes one path or the other
+constexpr size_t tile_wave_lds(int D, int R, int kern) {
+    return pair_ahead(D, R, kern) && (size_t)kParkBytes > sizeof(float) * (R + 1) * 64 ? (size_t)kParkBytes : sizeof(float) * (R + 1) * 64;
+}
+
 struct Tile {                                   // wave-uniform (SGPRs)
     int r0, r1, c0, c1;                         // cells whose sample lies in the GT box (bitmask == 1)
     int img, n, tile_r0, tile_c0;
@@ -1038,13 +1060,14 @@ __device__ __forceinline__ double total_weight_all_pairs(const InstArgs& a, cons
     return wave_total_f64(s);
 }
 
-// ---- tile wave (wave64, no LDS, no barrier) ------------------------------------------------------------------------------
+// ---- tile wave (wave64, no barrier; LDS only as the wave's own parking space, pair_ahead) -----------------------------------
 // Every UNORDERED pair is evaluated once and feeds both of its pixels: f(p,q) = f(q,p), the two weights W[k,p] + W[7-k,q]
 // share the colour predicate.  Per pixel (a, b) = (sigmoid(x), sigmoid(-x)), t = a - b, u = a b.  Per pair (p, q):
 //   S = a_p a_q + b_p b_q ; pw = -log S ; d pw / d x_p = -t_q u_p / S ; d pw / d x_q = -t_p u_q / S      (pairwise.cu:38-61)
 // S cannot underflow while every |x| <= 34; tiles with a larger logit take the log-space path.
-// Its waits: the predicate bytes of its own pixels (bit 7 set), when the logits have arrived and the per-pixel quantities are
-// computed; and, before the gradient goes out, sum W (the global normaliser, :1327-1328) = every predicate wave's arrival.  The
+// Its waits: the predicate bytes of its own pixels (bit 7 set), when the logits have arrived and the per-pixel quantities -- with
+// 4-row tiles at dilation 2 in the un-split single launch also S, log2 S and 1 / S of every pair (math_tile, phase A) -- are computed;
+// and, before the gradient goes out, sum W (the global normaliser, :1327-1328) = every predicate wave's arrival.  The
 // predicate waves precede the tile waves in the grid and never wait; by the time a tile wave asks they are normally done.
 // A tile wave's own few predicate words (written through by the predicate waves, which precede it in the grid), read past the
 // caches until every one carries this evaluation's tag; usually they are there at once.
@@ -1109,9 +1132,9 @@ __device__ __forceinline__ void tile_wave_arrives(const Ws& ws, int N, int wid, 
     }
 }
 
-template <int D, int R, bool ONE>
+template <int D, int R, bool ONE, int KERN>
 __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const Tile& t, float upw_warm, float n2max, int zero_bit, int n_items,
-                                          int spin_limit, float& scale, bool& have_scale, float* __restrict__ g_logits, float* gbuf /* LDS [R + 1][64] of this wave */,
+                                          int spin_limit, float& scale, bool& have_scale, float* __restrict__ g_logits, float* gbuf /* LDS of this wave: tile_wave_lds bytes */,
                                           int tix, long long& fx_sum, bool& bad_out, bool arrive, const LossState& st, float* __restrict__ losses) {
     constexpr int RD = TG<D, R>::RD;
     const int lane = threadIdx.x & 63;
@@ -1138,7 +1161,9 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
     float num = 0.f;
 #pragma unroll
     for (int j = 0; j < R; ++j) g[j] = 0.f;
-    // per-pixel quantities of this lane and of the lane D to its right: before the wait, they need the logits only
+    // What runs BEFORE the wait for the predicate words needs the logits only: the per-pixel quantities of this lane and of the lane D to its
+    // right (here) and, where pair_ahead says so, the pair terms S, log2 S, 1 / S (phase A below).  Behind the wait: the weights, then per pair
+    // two multiply-adds and the gradient products (phase B), the arrival.
     // PK (even dilation): rows 2k, 2k + 1 ride in the two halves of packed FP32 instructions (v_pk_mul / v_pk_fma: two pairs per instruction;
     // the conversions and the two transcendentals per pair stay scalar).  Every row's gradient receives the same terms in the same order.
     // 122 -> 106 registers at <2, 4>, 159 -> 138 at <2, 8>; 17.43 -> 17.07 us per evaluation at 32 instances (same box).  (The 8-row role
@@ -1168,6 +1193,47 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
     }
     }
     const bool slow = zero_bit != 0 || __any(sat);
+    // Phase A (pair_ahead): what a pair needs of the LOGITS alone -- S, log2 S, 1 / S, the two quarter-rate transcendentals per pair -- for every
+    // pair the loop below visits, in its order and with its expressions, BEFORE the wait for the predicate words: a wave that is resident before
+    // its words are there (the stream workgroups that stay on: most tile waves at 32 instances) does this arithmetic while it would otherwise
+    // idle, and between seeing the words and the arrival only the weights and the multiply-adds remain.  Parked per lane: the first kParkBytes /
+    // 64 bytes in the wave's LDS (slot s of lane l at [s][l]: nobody else reads it), the rest in registers -- the a / b planes that S needed are
+    // dead from here on, which is the room.  A wave whose words are already there runs A and B back to back and pays the parking traffic only.
+    constexpr bool AHEAD = pair_ahead(D, R, KERN);
+    static_assert(!AHEAD || (PK && D == 2), "the packed loop only; slot numbering below: direction 0 is skipped in the first step only");
+    constexpr int NSLOT = AHEAD ? 4 * ((R + D) / 2) - 1 : 0;                              // slot of (step, direction) = 4 step + direction - 1
+    constexpr int NPARK = kParkBytes / (64 * 16), NLDS = AHEAD ? (NSLOT < NPARK ? NSLOT : NPARK) : 0;      // slots in LDS: 16 bytes (two pairs) each
+    constexpr int NREG = AHEAD ? NSLOT - NLDS : 0;
+    typedef float v4 __attribute__((ext_vector_type(4)));
+    v2 klg2[NREG ? NREG : 1], krc2[NREG ? NREG : 1];
+    if constexpr (AHEAD) {
+        if (!slow) {
+            if constexpr (PK) {
+                v4* park = reinterpret_cast<v4*>(gbuf) + lane;
+#define BXI_AHEAD2(ip, ka, kb, qa, qb, dir)                                                                         \
+                {                                                                                                   \
+                    const int s = 4 * (ip) + (dir) - 1;                                                             \
+                    const v2 S = pa2[ka] * qa[kb] + pb2[ka] * qb[kb];                                               \
+                    const v2 lg = {__builtin_amdgcn_logf(S.x), __builtin_amdgcn_logf(S.y)};                         \
+                    const v2 rc = {__builtin_amdgcn_rcpf(S.x), __builtin_amdgcn_rcpf(S.y)};                         \
+                    if (s < NLDS) park[s * 64] = v4{lg.x, lg.y, rc.x, rc.y};                                        \
+                    else { klg2[s < NLDS ? 0 : s - NLDS] = lg; krc2[s < NLDS ? 0 : s - NLDS] = rc; }                \
+                }
+#pragma unroll
+                for (int ip = 0; ip < (R + D) / 2; ++ip) {
+                    const int jp = ip + D / 2;
+                    if (2 * ip >= D) BXI_AHEAD2(ip, ip, ip, aR2, bR2, 0)
+                    BXI_AHEAD2(ip, jp, ip, aR2, bR2, 1)
+                    BXI_AHEAD2(ip, ip, jp, pa2, pb2, 2)
+                    BXI_AHEAD2(ip, ip, jp, aR2, bR2, 3)
+                }
+#undef BXI_AHEAD2
+#pragma unroll
+                for (int k = 0; k < NREG; ++k) asm volatile("" : "+v"(klg2[k]), "+v"(krc2[k]));      // made HERE, not sunk behind the wait
+            }
+            asm volatile("" ::: "memory");        // the parked words are read back from the LDS behind the wait, not carried in registers across it
+        }
+    }
     bool bad = false;          // a bounded wait of this wave ran out (never expected): its arrival carries the fact to the finisher
     const int band0 = t.tile_r0 / kSBlk, band1 = (min(t.tile_r0 + R, h) - 1) / kSBlk;
     const bool look_early = !slow && (!have_scale || (ONE && g_logits));       // wave-uniform
@@ -1248,6 +1314,8 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
                 f1e = __hip_atomic_load(&ws.bandflag[(int64_t)n * ws.n_cb + band1], BXI_RLX, BXI_AGENT);
             }
         }
+        const v4* park2 = reinterpret_cast<const v4*>(gbuf) + lane;       // phase A's slots of this lane
+        (void)park2;
         // one unordered pair: A = (row ra, this lane) ; B = (row rb of the lane `q` names) ; num collects -log2 S
 #define BXI_PAIR(i, ra, rb, qa, qb, qt, qu, dir, GA, GB)                                                            \
         {                                                                                                           \
@@ -1268,10 +1336,17 @@ __device__ __forceinline__ void math_tile(const InstArgs& a, const Ws& ws, const
                 const uint32_t dwd = dw[dir][(2 * (ip)) >> 2] >> (8 * ((2 * (ip)) & 3));                              \
                 const v2 gw = {(float)(cwd & 255u), (float)((cwd >> 8) & 255u)};                                      \
                 const v2 nw = {(float)(dwd & 255u), (float)((dwd >> 8) & 255u)};                                      \
-                const v2 S = pa2[ka] * qa[kb] + pb2[ka] * qb[kb];                                                     \
-                const v2 lg = {__builtin_amdgcn_logf(S.x), __builtin_amdgcn_logf(S.y)};                               \
+                v2 lg, rc;                                                                                            \
+                if constexpr (AHEAD) {                                              /* phase B: parked by phase A */  \
+                    const int s = 4 * (ip) + (dir) - 1;                                                               \
+                    if (s < NLDS) { const v4 pk = park2[s * 64]; lg = v2{pk.x, pk.y}; rc = v2{pk.z, pk.w}; }          \
+                    else { lg = klg2[s < NLDS ? 0 : s - NLDS]; rc = krc2[s < NLDS ? 0 : s - NLDS]; }                  \
+                } else {                                                                                              \
+                    const v2 S = pa2[ka] * qa[kb] + pb2[ka] * qb[kb];                                                 \
+                    lg = v2{__builtin_amdgcn_logf(S.x), __builtin_amdgcn_logf(S.y)};                                  \
+                    rc = v2{__builtin_amdgcn_rcpf(S.x), __builtin_amdgcn_rcpf(S.y)};                                  \
+                }                                                                                                     \
                 num2 -= nw * lg;                                                                                      \
-                const v2 rc = {__builtin_amdgcn_rcpf(S.x), __builtin_amdgcn_rcpf(S.y)};                               \
                 const v2 mm = gw * rc;                                                                                \
                 GA -= mm * qt[kb] * pu2[ka];                                                                          \
                 GB -= mm * pt2[ka] * qu[kb];                                                                          \
@@ -1757,7 +1832,7 @@ __device__ __forceinline__ void finisher_role(const InstArgs& a, const Ws& ws, c
 }
 
 // tile workgroup: 4 independent waves striding through the tile list (its length is device data)
-template <int D, int R, bool ONE>
+template <int D, int R, bool ONE, int KERN>
 __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& vc, const Ws& ws, float upw_warm, float n2max, int zero_bit, int n_items, int spin_limit,
                                           float* __restrict__ g_logits, unsigned char* smem, int tblk, int n_tb, const LossState& st, float* __restrict__ losses) {
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
@@ -1797,7 +1872,7 @@ __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& v
     // does run out: as loud)
     if (!ok) { tile_wave_arrives(ws, N, wid, 0, true); return; }
     const int total = N < 64 ? __builtin_amdgcn_readlane(e0.x, N < 64 ? N : 0) : __builtin_amdgcn_readfirstlane(eN.x);
-    float* gbuf = reinterpret_cast<float*>(smem) + wave * ((R + 1) * 64);
+    float* gbuf = reinterpret_cast<float*>(smem + wave * tile_wave_lds(D, R, KERN));
     float scale = 0.f;
     bool have_scale = false, bad = false;
     long long fx_sum = 0;
@@ -1815,7 +1890,7 @@ __device__ __forceinline__ void tile_role(const InstArgs& a, const ValidCells& v
         if (!locate_tile<D, R, ONE>(ws, vc, N, e0, e1, ti, a.h, a.w, spin_limit, t)) { bad = true; break; }
         BXI_TW(1, wid, 1);
         const bool last = may_arrive_early && ti + nwaves >= total;
-        math_tile<D, R, ONE>(a, ws, t, upw_warm, n2max, zero_bit, n_items, spin_limit, scale, have_scale, g_logits, gbuf, wid, fx_sum, bad, last, st, losses);
+        math_tile<D, R, ONE, KERN>(a, ws, t, upw_warm, n2max, zero_bit, n_items, spin_limit, scale, have_scale, g_logits, gbuf, wid, fx_sum, bad, last, st, losses);
         arrived = last;
     }
     if (!arrived) tile_wave_arrives(ws, N, wid, fx_sum, bad);
@@ -1900,7 +1975,7 @@ __global__ __launch_bounds__(256, pair_occ(D, R)) void pair_kernel(const float* 
         BXI_TW(3, 1 + blk - lead0, 0);
         leader_block<false>(a, D, ws, st, blk - lead0, upp, g_logits, smem, red, spin_limit);
     } else {
-        tile_role<D, R, false>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, zero_bit, n_items, spin_limit, g_logits, smem, blk - tile0, n_tb, st, losses);
+        tile_role<D, R, false, kTilesPair>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, zero_bit, n_items, spin_limit, g_logits, smem, blk - tile0, n_tb, st, losses);
     }
 }
 
@@ -2013,7 +2088,7 @@ __global__ __launch_bounds__(256, (R == 4 ? kOneOcc : kLongOcc)) void eval1_kern
     }
     if (role == 4) {          // ONE call site for the stream workgroups that stay on and for the tile workgroups proper
         const int shift = merge ? n_stream : 0;
-        tile_role<D, R, true>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, 0, n_items, spin_limit, g_logits, smem, idx + shift, n_tb + shift, st, losses);
+        tile_role<D, R, true, (READY ? kTilesOneReady : kTilesOne)>(a, vc, ws, upw * resolve_warmup(warmup, st.iter), n2max, 0, n_items, spin_limit, g_logits, smem, idx + shift, n_tb + shift, st, losses);
         return;
     }
     finisher_role<true>(a, ws, st, upp, upw, resolve_warmup(warmup, st.iter), 0, n_items, spin_limit, R, (n_tb + (merge ? n_stream : 0)) * kWaves, losses);
@@ -2385,7 +2460,9 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     const int n_tab = ((a.N + 64) / 64 + kWaves - 1) / kWaves;
     const int n_stream = a.N * ((a.h + kSBlk - 1) / kSBlk);
     const size_t lds_stream = std::max(kPoolLds, 8 * (size_t)kWaves * a.w);
-    const size_t lds_pair = std::max(sizeof(float) * (size_t)kWaves * (R + 1) * 64, 2 * sizeof(float) * (size_t)(a.h + a.w) + 16);
+    // (the tile waves' share is tile_wave_lds: each kernel parks its pair terms or does not)
+    auto lds_pair_of = [&](int kern) { return std::max((size_t)kWaves * tile_wave_lds(dil, R, kern), 2 * sizeof(float) * (size_t)(a.h + a.w) + 16); };
+    const size_t lds_pair = lds_pair_of(kTilesPair);
     const int cus = stream_cus(s, device_cus());                      // a CU-masked stream has fewer
     const bool whole_device = cus >= device_cus();
 
@@ -2405,7 +2482,7 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     // (targets ready: the short single launch while its stream workgroups are a quarter of the slots -- 14.1 vs 14.4-14.9 us for two launches at 32
     // instances; at 64 two launches take 18.3 against 18.7 us: R6-14)
     const bool short_ok = one_fits && !(ready && 4 * (int64_t)n_stream > one_slots);
-    const size_t lds_one = std::max(lds_stream, lds_pair);
+    const size_t lds_one = std::max(lds_stream, lds_pair_of(ready ? kTilesOneReady : kTilesOne));
     if (!(flags & kFlagTwo) && (short_ok || (flags & kFlagSingle) || long_form) && !head && pooled_in_launch && (R == 4 || long_form) && dil <= 2 &&
         !pr.zero_bit && lds_one <= 36 * 1024) {                       // (four workgroups per CU must fit)
         const int slots = long_form ? kLongOcc * device_cus() : one_slots;
