@@ -20,6 +20,10 @@ Public surface (mirrors the reference's for this path):
     condinst_box_targets               <-> CondInstBoxHead.get_targets / centerness_target (FCOS assignment of a whole batch, one launch)
     condinst_box_loss                  <-> CondInstBoxHead.loss (focal, IoU / GIoU and centerness loss with gradients, no sync)
     parse_box_head_cfg                 : the bbox_head block of the reference's configs as condinst_box_loss takes it
+    solov2_targets                     <-> DiscoBoxSOLOv2Head.solov2_target_single over a batch (mask pass + assignment, one sync)
+    box_solov2_targets                 <-> BoxSOLOv2Head.solo_target_single over a batch (without its two F.interpolate)
+    solo_cate_loss                     <-> loss_cate of both SOLOv2-style heads (focal loss on the NCHW maps, avg_factor on the device)
+    parse_solo_head_cfg                : the bbox_head block of configs/discobox and configs/boxlevelset as the functions take it
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -33,6 +37,7 @@ from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask
 from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigner, box2mask_get_targets
 from .box_nms import batched_nms, condinst_get_bboxes, nms, nms_with_others
 from .box_head_loss import condinst_box_loss, condinst_box_targets, parse_box_head_cfg
+from .solo_targets import SoloTargets, box_solov2_targets, parse_solo_head_cfg, solo_cate_loss, solov2_targets
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -44,5 +49,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single',
            'ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'box2mask_get_targets', 'MATCH_COST', 'BBOX_ASSIGNERS',
            'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes',
-           'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg']
+           'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg',
+           'solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets']
 __version__ = '0.1.0'

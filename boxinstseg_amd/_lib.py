@@ -206,6 +206,23 @@ FCOS_SIGNATURES = {
                                           c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_solo.h (training targets of the SOLOv2-style heads and their category loss); applied by load() as well
+SOLO_MODES = {'discobox': 0, 'boxlevelset': 1}
+SOLO_MAX_FACTORS, SOLO_MAX_FACTOR, SOLO_RESCALE_MIN_ONES, SOLO_MIN_MASK_SUM, SOLO_MAX_GRID, SOLO_PAIRS_PER_INSTANCE = 4, 64, 2, 10, 64, 9
+SOLO_STATUS_BAD_LABEL = 1
+SOLO_SIGNATURES = {
+    'bxi_solo_mask_pass_u8': (c_int, [C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int), c_int, C.POINTER(c_int),
+                                      C.POINTER(c_int), C.POINTER(c_int), c_int, C.POINTER(c_void_p), c_void_p, c_void_p]),
+    'bxi_solo_assign_f32': (c_int, [c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_float), C.c_double, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, C.POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    'bxi_solo_cate_workspace_bytes': (c_size_t, [C.POINTER(c_int), c_int, c_int, c_int]),
+    'bxi_solo_cate_loss_f32': (c_int, [C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_float,
+                                       C.POINTER(c_void_p), c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_solo_cate_grad_rescale_f32': (c_int, [C.POINTER(c_int), c_int, c_int, c_int, C.POINTER(c_void_p), c_void_p, C.POINTER(c_void_p),
+                                               c_void_p]),
+}
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -227,7 +244,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         for name, (res, args) in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + \
-                list(DET_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()):
+                list(DET_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(SOLO_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,162 @@
+// focal_device.hpp -- what the two training-loss files share (fcos_loss.hip, solo_targets.hip): the (level, image, tile) grid of the
+// flattened training order, the flat segment grid, the fixed-order workgroup sums, the sigmoid focal loss of one logit with its
+// derivative, and the flat rescale kernel of the backward step.  Everything sits in an unnamed namespace: each file has its own copy.
+#pragma once
+
+#include <float.h>
+#include <math.h>
+
+#include "common.hpp"
+#include "../../include/boxinst/boxinst_hip_fcos.h"
+
+// The rounded-operation intrinsics of the HIP headers are plain operators there, and the compiler may still contract a product and
+// a sum that meet after inlining.  Nothing in these files is contracted: the single fp32 operations are what the bit-equal targets rest on.
+#pragma clang fp contract(off)
+
+namespace bxi {
+namespace {
+
+__device__ __forceinline__ float f_add(float a, float b) { return a + b; }
+__device__ __forceinline__ float f_sub(float a, float b) { return a - b; }
+__device__ __forceinline__ float f_mul(float a, float b) { return a * b; }
+__device__ __forceinline__ float f_div(float a, float b) { return a / b; }
+
+constexpr int kLocTile = BXI_FCOS_LOC_TILE;
+constexpr int kElemTile = BXI_FCOS_ELEM_TILE;
+constexpr int kMaxL = BXI_DET_MAX_LEVELS;
+
+// the per-location grid: workgroup -> (level, image, tile)
+struct LocGrid {
+    int H[kMaxL], W[kMaxL], stride[kMaxL];
+    int first[kMaxL + 1];       // locations of one image in the levels before l
+    int tiles[kMaxL];           // ceil(H*W / kLocTile)
+    int blk_first[kMaxL + 1];   // first workgroup of level l; blk_first[n] = number of workgroups
+    int n, B;
+};
+// flat segments: workgroup -> (segment, tile of kElemTile elements)
+struct FlatGrid {
+    int count[3 * kMaxL];           // elements of segment s
+    int blk_first[3 * kMaxL + 1];
+    int n;                          // segments
+};
+
+// workgroup sums in a fixed order: the DPP wave total, then the four waves pairwise (thread 0 holds the result)
+__device__ __forceinline__ double block_sum_f64(double v, double* s4) {
+    v = wave_total_f64(v);
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double r = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ int block_sum_i32(int v, int* s4) {
+    v = wave_total_i32(v);
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int r = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    __syncthreads();
+    return r;
+}
+
+// ---- focal loss -----------------------------------------------------------------------------------------------------------
+template <bool G2>
+__device__ __forceinline__ void focal_one(float x, bool t, float gamma, float alpha, float scale, float& loss, float& grad) {
+    const float e = expf(-fabsf(x));
+    const float inv = 1.f / (1.f + e);
+    const float big = inv, small = e * inv;                 // sigmoid(|x|), sigmoid(-|x|)
+    const float p = x >= 0.f ? big : small, q = x >= 0.f ? small : big;    // sigmoid(x), 1 - sigmoid(x) without cancellation
+    const float bce = fmaxf(t ? -x : x, 0.f) + log1pf(e);   // max(x,0) - x t + log1p(exp(-|x|))
+    const float pt = t ? q : p;
+    float mod, dmod;
+    if (G2) {
+        mod = pt * pt;
+        dmod = 2.f * pt;
+    } else {
+        mod = powf(pt, gamma);
+        dmod = gamma == 0.f ? 0.f : gamma * powf(pt, gamma - 1.f);
+    }
+    const float aw = t ? alpha : 1.f - alpha;
+    const float dpt = t ? -(p * q) : p * q;
+    loss = aw * bce * mod;
+    grad = scale * aw * ((t ? -q : p) * mod + bce * dmod * dpt);           // d bce / dx = sigmoid(x) - t
+}
+
+// ---- backward rescale -----------------------------------------------------------------------------------------------------
+struct RescaleSegs { const float* src[3 * kMaxL]; float* dst[3 * kMaxL]; int which[3 * kMaxL]; };
+
+__global__ __launch_bounds__(256) void flat_rescale_kernel(RescaleSegs sg, FlatGrid f, const float* __restrict__ upstream) {
+    const int blk = blockIdx.x;
+    int s = 0;
+    while (s + 1 < f.n && blk >= f.blk_first[s + 1]) ++s;
+    const int count = f.count[s];
+    const int e0 = (blk - f.blk_first[s]) * kElemTile + threadIdx.x * 4;
+    if (e0 >= count) return;
+    const float* src = sg.src[s];
+    float* dst = sg.dst[s];
+    const float u = upstream[sg.which[s]];
+    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && e0 + 3 < count) {
+        float4 q = *reinterpret_cast<const float4*>(src + e0);
+        q.x *= u; q.y *= u; q.z *= u; q.w *= u;
+        *reinterpret_cast<float4*>(dst + e0) = q;
+    } else {
+        for (int j = 0; j < 4 && e0 + j < count; ++j) dst[e0 + j] = src[e0 + j] * u;
+    }
+}
+
+// ---- host ----------------------------------------------------------------------------------------------------------------
+int make_grid(const int* H, const int* W, const int* stride, int n_levels, int B, LocGrid& g) {
+    if (n_levels < 1 || n_levels > kMaxL || B < 0 || B > BXI_MAX_IMAGES) return BXI_ERR_BAD_SHAPE;
+    g.n = n_levels;
+    g.B = B;
+    int64_t at = 0, blk = 0;
+    for (int l = 0; l < kMaxL; ++l) {
+        if (l < n_levels) {
+            if (H[l] < 1 || W[l] < 1 || stride[l] < 1) return BXI_ERR_BAD_SHAPE;
+            const int64_t hw = (int64_t)H[l] * W[l];
+            if (!fits_i32(hw)) return BXI_ERR_BAD_SHAPE;
+            g.H[l] = H[l]; g.W[l] = W[l]; g.stride[l] = stride[l];
+            g.first[l] = (int)at;
+            g.tiles[l] = (int)((hw + kLocTile - 1) / kLocTile);
+            g.blk_first[l] = (int)blk;
+            at += hw;
+            blk += (int64_t)B * g.tiles[l];
+            if (!fits_i32(at * (B > 0 ? B : 1) * 4) || !fits_i32(blk)) return BXI_ERR_BAD_SHAPE;
+        } else {
+            g.H[l] = g.W[l] = g.stride[l] = 1;
+            g.first[l] = (int)at;
+            g.tiles[l] = 1;
+            g.blk_first[l] = (int)blk;
+        }
+    }
+    g.first[kMaxL] = (int)at;
+    g.blk_first[kMaxL] = (int)blk;
+    for (int l = n_levels; l <= kMaxL; ++l) { g.first[l] = (int)at; g.blk_first[l] = (int)blk; }
+    return BXI_OK;
+}
+
+// segments of `per_level` maps with `chan[k]` channels each; returns the number of workgroups or -1
+int64_t make_flat(const LocGrid& g, const int* chan, int per_level, FlatGrid& f) {
+    f.n = g.n * per_level;
+    int64_t blk = 0;
+    for (int s = 0; s < 3 * kMaxL; ++s) {
+        f.blk_first[s] = (int)blk;
+        if (s < f.n) {
+            const int l = s / per_level, k = s - l * per_level;
+            const int64_t cnt = (int64_t)g.B * chan[k] * g.H[l] * g.W[l];
+            if (!fits_i32(cnt)) return -1;
+            f.count[s] = (int)cnt;
+            blk += (cnt + kElemTile - 1) / kElemTile;
+            if (!fits_i32(blk)) return -1;
+        } else {
+            f.count[s] = 0;
+        }
+    }
+    f.blk_first[3 * kMaxL] = (int)blk;
+    for (int s = f.n; s <= 3 * kMaxL; ++s) f.blk_first[s] = (int)blk;
+    return blk;
+}
+
+bool workspace_ok(const void* ws, size_t have, size_t need) { return ws && have >= need && !(reinterpret_cast<uintptr_t>(ws) & 3); }
+
+}  // namespace
+}  // namespace bxi
