@@ -132,7 +132,7 @@ SIGNATURES = {
                                                     c_void_p, c_size_t, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_post.h (test-time post-processing of the SOLOv2-style heads); applied by load() next to SIGNATURES
+# include/boxinst/boxinst_hip_post.h (test-time post-processing of the SOLOv2-style heads)
 NMS_KERNELS = {'gaussian': 0, 'linear': 1}
 NMS_MAX_CANDIDATES = 2048
 POST_SIGNATURES = {
@@ -143,7 +143,7 @@ POST_SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_assign.h (Box2Mask target assignment: matching cost and Hungarian); applied by load() as well
+# include/boxinst/boxinst_hip_assign.h (Box2Mask target assignment: matching cost and Hungarian)
 MATCH_MAX_SIDE = 1024
 MATCH_STATUS_NONFINITE, MATCH_STATUS_BAD_LABEL = 1, 2
 ASSIGN_SIGNATURES = {
@@ -158,7 +158,7 @@ ASSIGN_SIGNATURES = {
                                               c_void_p, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_det.h (CondInst test-time detections: decode, score filter, box NMS); applied by load() as well
+# include/boxinst/boxinst_hip_det.h (CondInst test-time detections: decode, score filter, box NMS)
 DET_MAX_LEVELS, DET_SORT_MAX, DET_NMS_ROUND, DET_KEEP_TILE, DET_ROW_TILE = 8, 16384, 256, 2048, 64
 DET_STATUS_OVER_CAP, DET_STATUS_OVER_SORT, DET_STATUS_BAD_ORDER = 1, 2, 4
 
@@ -180,7 +180,7 @@ DET_SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_fcos.h (the box head's training step: FCOS targets, focal / IoU / centerness loss); applied by load() as well
+# include/boxinst/boxinst_hip_fcos.h (the box head's training step: FCOS targets, focal / IoU / centerness loss)
 FCOS_GT_CHUNK, FCOS_LOC_TILE, FCOS_ELEM_TILE, FCOS_STATUS_BAD_LABEL = 64, 256, 1024, 1
 FCOS_BBOX_KINDS = {'giou': 0, 'iou_log': 1, 'iou_linear': 2, 'iou_square': 3}
 
@@ -206,7 +206,7 @@ FCOS_SIGNATURES = {
                                           c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_solo.h (training targets of the SOLOv2-style heads and their category loss); applied by load() as well
+# include/boxinst/boxinst_hip_solo.h (training targets of the SOLOv2-style heads and their category loss)
 SOLO_MODES = {'discobox': 0, 'boxlevelset': 1}
 SOLO_MAX_FACTORS, SOLO_MAX_FACTOR, SOLO_RESCALE_MIN_ONES, SOLO_MIN_MASK_SUM, SOLO_MAX_GRID, SOLO_PAIRS_PER_INSTANCE = 4, 64, 2, 10, 64, 9
 SOLO_STATUS_BAD_LABEL = 1
@@ -222,6 +222,17 @@ SOLO_SIGNATURES = {
     'bxi_solo_cate_grad_rescale_f32': (c_int, [C.POINTER(c_int), c_int, c_int, c_int, C.POINTER(c_void_p), c_void_p, C.POINTER(c_void_p),
                                                c_void_p]),
 }
+
+# every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
+# applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
+FAMILIES = [
+    ('base', ('include/boxinst_hip.h', 'include/boxinst_hip_dev.h'), SIGNATURES),
+    ('post', ('include/boxinst/boxinst_hip_post.h',), POST_SIGNATURES),
+    ('assign', ('include/boxinst/boxinst_hip_assign.h',), ASSIGN_SIGNATURES),
+    ('det', ('include/boxinst/boxinst_hip_det.h',), DET_SIGNATURES),
+    ('fcos', ('include/boxinst/boxinst_hip_fcos.h',), FCOS_SIGNATURES),
+    ('solo', ('include/boxinst/boxinst_hip_solo.h',), SOLO_SIGNATURES),
+]
 
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
@@ -243,11 +254,14 @@ def load() -> C.CDLL:
                 '(run `python -c "import __graft_entry__ as g; g.build()"` or `python -m boxinstseg_amd.build`). '
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()) + list(ASSIGN_SIGNATURES.items()) + \
-                list(DET_SIGNATURES.items()) + list(FCOS_SIGNATURES.items()) + list(SOLO_SIGNATURES.items()):
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        owner = {}
+        for family, _, table in FAMILIES:
+            for name, (res, args) in table.items():
+                if owner.setdefault(name, family) != family:
+                    raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
         if lib.bxi_abi_version() != BXI_ABI_VERSION:
             raise RuntimeError(f'{path}: ABI version {lib.bxi_abi_version()} != {BXI_ABI_VERSION}')
         _lib = lib

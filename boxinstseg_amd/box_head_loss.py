@@ -28,6 +28,7 @@ import torch
 
 from . import _lib
 from . import dist as _dist
+from ._common import cfg_get, cfg_only, current_stream, need_cuda
 
 __all__ = ['condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg', 'BoxTargets', 'INF', 'GT_CHUNK']
 
@@ -39,94 +40,68 @@ BoxTargets = namedtuple('BoxTargets', ['labels', 'bbox_targets', 'gt_inds', 'poi
                                        'status'])
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
-
-
-def _get(cfg, name, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(name, default)
-    return getattr(cfg, name, default)
-
-
-def _keys(cfg):
-    return list(cfg.keys()) if isinstance(cfg, dict) else [k for k in vars(cfg) if not k.startswith('_')]
-
-
-def _only(cfg, where, allowed):
-    for k in _keys(cfg):
-        if k not in allowed:
-            raise NotImplementedError(f'{where}.{k} is not supported')
-
-
 def parse_box_head_cfg(cfg):
     """``bbox_head=dict(type='CondInstBoxHead', ...)`` (dict or namespace) -> the flat settings ``condinst_box_loss`` takes:
     num_classes, strides, regress_ranges, center_sampling, center_sample_radius, norm_on_bbox, gamma, alpha, loss_weight_cls,
     bbox_loss_kind, eps, loss_weight_bbox, loss_weight_centerness.  Keys that only shape the network (in_channels, stacked_convs,
     feat_channels, ...) are accepted and ignored.  A loss type or option that is not built raises NotImplementedError naming the key."""
-    kind = _get(cfg, 'type', 'CondInstBoxHead')
+    kind = cfg_get(cfg, 'type', 'CondInstBoxHead')
     if kind != 'CondInstBoxHead':
         raise NotImplementedError(f"bbox_head.type {kind!r} is not supported: only 'CondInstBoxHead'")
-    num_classes = _get(cfg, 'num_classes')
+    num_classes = cfg_get(cfg, 'num_classes')
     if num_classes is None:
         raise TypeError('bbox_head has no `num_classes`')
-    strides = _get(cfg, 'strides', (4, 8, 16, 32, 64))
+    strides = cfg_get(cfg, 'strides', (4, 8, 16, 32, 64))
     strides = [int(s[0] if isinstance(s, (tuple, list)) else s) for s in strides]
-    ranges = _get(cfg, 'regress_ranges', DEFAULT_REGRESS_RANGES)
+    ranges = cfg_get(cfg, 'regress_ranges', DEFAULT_REGRESS_RANGES)
     ranges = tuple((float(a), float(b)) for a, b in ranges)
     if len(ranges) != len(strides):
         raise TypeError(f'{len(strides)} strides but {len(ranges)} regress_ranges')
 
-    lc = _get(cfg, 'loss_cls', dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0))
-    if _get(lc, 'type') != 'FocalLoss':
-        raise NotImplementedError(f"loss_cls.type {_get(lc, 'type')!r} is not supported: only 'FocalLoss'")
-    _only(lc, 'loss_cls', ('type', 'use_sigmoid', 'gamma', 'alpha', 'loss_weight', 'reduction', 'activated'))
-    if not _get(lc, 'use_sigmoid', True):
+    lc = cfg_get(cfg, 'loss_cls', dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0))
+    if cfg_get(lc, 'type') != 'FocalLoss':
+        raise NotImplementedError(f"loss_cls.type {cfg_get(lc, 'type')!r} is not supported: only 'FocalLoss'")
+    cfg_only(lc, 'loss_cls', ('type', 'use_sigmoid', 'gamma', 'alpha', 'loss_weight', 'reduction', 'activated'))
+    if not cfg_get(lc, 'use_sigmoid', True):
         raise NotImplementedError('loss_cls.use_sigmoid=False is not supported')
-    if _get(lc, 'activated', False):
+    if cfg_get(lc, 'activated', False):
         raise NotImplementedError('loss_cls.activated=True is not supported')
-    if _get(lc, 'reduction', 'mean') != 'mean':
+    if cfg_get(lc, 'reduction', 'mean') != 'mean':
         raise NotImplementedError("loss_cls.reduction: only 'mean' is supported")
 
-    lb = _get(cfg, 'loss_bbox', dict(type='IoULoss', loss_weight=1.0))
-    bt = _get(lb, 'type')
+    lb = cfg_get(cfg, 'loss_bbox', dict(type='IoULoss', loss_weight=1.0))
+    bt = cfg_get(lb, 'type')
     if bt == 'GIoULoss':
-        _only(lb, 'loss_bbox', ('type', 'eps', 'reduction', 'loss_weight'))
+        cfg_only(lb, 'loss_bbox', ('type', 'eps', 'reduction', 'loss_weight'))
         bbox_kind = 'giou'
     elif bt == 'IoULoss':
-        _only(lb, 'loss_bbox', ('type', 'linear', 'eps', 'reduction', 'loss_weight', 'mode'))
-        mode = 'linear' if _get(lb, 'linear', False) else _get(lb, 'mode', 'log')
+        cfg_only(lb, 'loss_bbox', ('type', 'linear', 'eps', 'reduction', 'loss_weight', 'mode'))
+        mode = 'linear' if cfg_get(lb, 'linear', False) else cfg_get(lb, 'mode', 'log')
         if mode not in ('log', 'linear', 'square'):
             raise NotImplementedError(f'loss_bbox.mode {mode!r} is not supported')
         bbox_kind = 'iou_' + mode
     else:
         raise NotImplementedError(f"loss_bbox.type {bt!r} is not supported: only 'GIoULoss' and 'IoULoss'")
-    if _get(lb, 'reduction', 'mean') != 'mean':
+    if cfg_get(lb, 'reduction', 'mean') != 'mean':
         raise NotImplementedError("loss_bbox.reduction: only 'mean' is supported")
 
-    ln = _get(cfg, 'loss_centerness', dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0))
-    if _get(ln, 'type') != 'CrossEntropyLoss':
-        raise NotImplementedError(f"loss_centerness.type {_get(ln, 'type')!r} is not supported: only 'CrossEntropyLoss'")
-    _only(ln, 'loss_centerness', ('type', 'use_sigmoid', 'use_mask', 'reduction', 'class_weight', 'loss_weight'))
-    if not _get(ln, 'use_sigmoid', False) or _get(ln, 'use_mask', False):
+    ln = cfg_get(cfg, 'loss_centerness', dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0))
+    if cfg_get(ln, 'type') != 'CrossEntropyLoss':
+        raise NotImplementedError(f"loss_centerness.type {cfg_get(ln, 'type')!r} is not supported: only 'CrossEntropyLoss'")
+    cfg_only(ln, 'loss_centerness', ('type', 'use_sigmoid', 'use_mask', 'reduction', 'class_weight', 'loss_weight'))
+    if not cfg_get(ln, 'use_sigmoid', False) or cfg_get(ln, 'use_mask', False):
         raise NotImplementedError('loss_centerness: only use_sigmoid=True (binary cross entropy with logits) is supported')
-    if _get(ln, 'class_weight') is not None:
+    if cfg_get(ln, 'class_weight') is not None:
         raise NotImplementedError('loss_centerness.class_weight is not supported')
-    if _get(ln, 'reduction', 'mean') != 'mean':
+    if cfg_get(ln, 'reduction', 'mean') != 'mean':
         raise NotImplementedError("loss_centerness.reduction: only 'mean' is supported")
 
     return dict(num_classes=int(num_classes), strides=strides, regress_ranges=ranges,
-                center_sampling=bool(_get(cfg, 'center_sampling', True)), center_sample_radius=float(_get(cfg, 'center_sample_radius', 1.5)),
-                norm_on_bbox=bool(_get(cfg, 'norm_on_bbox', True)),
-                gamma=float(_get(lc, 'gamma', 2.0)), alpha=float(_get(lc, 'alpha', 0.25)), loss_weight_cls=float(_get(lc, 'loss_weight', 1.0)),
-                bbox_loss_kind=bbox_kind, eps=float(_get(lb, 'eps', 1e-6)), loss_weight_bbox=float(_get(lb, 'loss_weight', 1.0)),
-                loss_weight_centerness=float(_get(ln, 'loss_weight', 1.0)))
+                center_sampling=bool(cfg_get(cfg, 'center_sampling', True)), center_sample_radius=float(cfg_get(cfg, 'center_sample_radius', 1.5)),
+                norm_on_bbox=bool(cfg_get(cfg, 'norm_on_bbox', True)),
+                gamma=float(cfg_get(lc, 'gamma', 2.0)), alpha=float(cfg_get(lc, 'alpha', 0.25)), loss_weight_cls=float(cfg_get(lc, 'loss_weight', 1.0)),
+                bbox_loss_kind=bbox_kind, eps=float(cfg_get(lb, 'eps', 1e-6)), loss_weight_bbox=float(cfg_get(lb, 'loss_weight', 1.0)),
+                loss_weight_centerness=float(cfg_get(ln, 'loss_weight', 1.0)))
 
 
 _FLAT_KEYS = ('num_classes', 'strides', 'regress_ranges', 'center_sampling', 'center_sample_radius', 'norm_on_bbox', 'gamma', 'alpha',
@@ -187,7 +162,7 @@ def condinst_box_targets(featmap_sizes, strides, gt_bboxes, gt_labels, *, regres
         raise RuntimeError(f'{B} images but {len(gt_bboxes)} gt_bboxes and {len(gt_labels)} gt_labels')
     if not 1 <= B <= _lib.BXI_MAX_IMAGES:
         raise RuntimeError(f'B must be in 1..{_lib.BXI_MAX_IMAGES}, got {B}')
-    _need_cuda(**{f'gt_bboxes[{i}]': t for i, t in enumerate(gt_bboxes)}, **{f'gt_labels[{i}]': t for i, t in enumerate(gt_labels)})
+    need_cuda(**{f'gt_bboxes[{i}]': t for i, t in enumerate(gt_bboxes)}, **{f'gt_labels[{i}]': t for i, t in enumerate(gt_labels)})
     arr, sizes = _fcos_levels(featmap_sizes, strides)
     n = len(sizes)
     if len(regress_ranges) != n:
@@ -213,7 +188,7 @@ def condinst_box_targets(featmap_sizes, strides, gt_bboxes, gt_labels, *, regres
             None if boxes is None else boxes.data_ptr(), None if labs is None else labs.data_ptr(), _lib.int_array(offsets),
             out.labels.data_ptr(), out.bbox_targets.data_ptr(), out.gt_inds.data_ptr(), out.points.data_ptr(), out.level_inds.data_ptr(),
             out.img_inds.data_ptr(), out.ctr_targets.data_ptr(), out.stats.data_ptr(), out.status.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-            _stream(dev)))
+            current_stream(dev)))
     return out
 
 
@@ -245,7 +220,7 @@ class _BoxHeadLoss(torch.autograd.Function):
             _lib.check('bxi_fcos_loss_f32', _lib.load().bxi_fcos_loss_f32(
                 lv, n, B, C, tg.labels.data_ptr(), tg.bbox_targets.data_ptr(), tg.ctr_targets.data_ptr(), norm.data_ptr(), s['gamma'], s['alpha'],
                 s['loss_weight_cls'], s['loss_weight_bbox'], s['loss_weight_centerness'], _lib.FCOS_BBOX_KINDS[s['bbox_loss_kind']], s['eps'],
-                _grads_array(unit), losses.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)))
+                _grads_array(unit), losses.data_ptr(), ws.data_ptr(), ws.numel() * 4, current_stream(dev)))
         ctx.unit, ctx.fl, ctx.n, ctx.B, ctx.C = unit, fl, n, B, C
         return losses
 
@@ -257,7 +232,7 @@ class _BoxHeadLoss(torch.autograd.Function):
         out = tuple([torch.empty_like(t) for t in part] for part in unit)
         with torch.cuda.device(dev):
             _lib.check('bxi_fcos_grad_rescale_f32', _lib.load().bxi_fcos_grad_rescale_f32(
-                ctx.fl, n, ctx.B, ctx.C, _grads_array(unit), up.data_ptr(), _grads_array(out), _stream(dev)))
+                ctx.fl, n, ctx.B, ctx.C, _grads_array(unit), up.data_ptr(), _grads_array(out), current_stream(dev)))
         return (None, None, None, None, *out[0], *out[1], *out[2])
 
 
@@ -279,7 +254,7 @@ def condinst_box_loss(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels
         raise RuntimeError(f'1..{_lib.DET_MAX_LEVELS} levels with cls, bbox and centerness each, got {n}, {len(bbox_preds)}, {len(centernesses)}')
     if len(s['strides']) != n:
         raise RuntimeError(f"{n} levels but {len(s['strides'])} strides")
-    _need_cuda(**{f'cls_scores[{i}]': t for i, t in enumerate(cls_scores)}, **{f'bbox_preds[{i}]': t for i, t in enumerate(bbox_preds)},
+    need_cuda(**{f'cls_scores[{i}]': t for i, t in enumerate(cls_scores)}, **{f'bbox_preds[{i}]': t for i, t in enumerate(bbox_preds)},
                **{f'centernesses[{i}]': t for i, t in enumerate(centernesses)})
     for name, v in (('gamma', s['gamma']), ('alpha', s['alpha']), ('eps', s['eps'])):
         if math.isnan(v):

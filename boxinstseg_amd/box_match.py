@@ -18,20 +18,11 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._common import current_stream, need_cuda, ptr
 from .registry import BBOX_ASSIGNERS, MATCH_COST, build_match_cost
 
 __all__ = ['ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'AssignResult', 'box2mask_get_targets',
            'project_pred', 'project_gt', 'match_cost', 'linear_sum_assignment']
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
 
 
 def _offsets(counts):
@@ -55,7 +46,7 @@ def project_pred(logits: torch.Tensor, target_shape=None, act: bool = True):
     """``logits`` [n,h,w] fp32 -> (proj_rows [n,H], proj_cols [n,W], sumsq [n,2]) of the predictions bilinearly sampled at
     ``target_shape`` = (H, W) (``align_corners=False``; None: the logits' own size): the maximum of every row and of every column, after
     the sigmoid when ``act``, and the sum of squares of each projection.  Nothing of size n*H*W is allocated."""
-    _need_cuda(logits=logits)
+    need_cuda(logits=logits)
     if logits.dim() != 3 or logits.dtype != torch.float32:
         raise RuntimeError(f'logits must be fp32 [n,h,w], got {logits.dtype} {tuple(logits.shape)}')
     dev = logits.device
@@ -67,7 +58,7 @@ def project_pred(logits: torch.Tensor, target_shape=None, act: bool = True):
     with torch.cuda.device(dev):
         _lib.check('bxi_match_project_pred_f32', _lib.load().bxi_match_project_pred_f32(
             x.data_ptr(), n, h, w, H, W, 1 if act else 0, rows.data_ptr(), cols.data_ptr(), sumsq.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-            _stream(dev)))
+            current_stream(dev)))
     return rows, cols, sumsq
 
 
@@ -80,16 +71,16 @@ def _project_gt_into(masks, rows, cols, sumsq, ws):
         if m.dtype in (torch.bool, torch.uint8):
             m = m.view(torch.uint8) if m.dtype == torch.bool else m
             _lib.check('bxi_match_project_gt_u8', lib.bxi_match_project_gt_u8(
-                m.data_ptr(), g, H, W, rows.data_ptr(), cols.data_ptr(), sumsq.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)))
+                m.data_ptr(), g, H, W, rows.data_ptr(), cols.data_ptr(), sumsq.data_ptr(), ws.data_ptr(), ws.numel() * 4, current_stream(dev)))
         else:
             m = m.to(torch.float32)
             _lib.check('bxi_match_project_gt_f32', lib.bxi_match_project_gt_f32(
-                m.data_ptr(), g, H, W, rows.data_ptr(), cols.data_ptr(), sumsq.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)))
+                m.data_ptr(), g, H, W, rows.data_ptr(), cols.data_ptr(), sumsq.data_ptr(), ws.data_ptr(), ws.numel() * 4, current_stream(dev)))
 
 
 def project_gt(masks: torch.Tensor):
     """``masks`` [g,H,W] bool / uint8 / float -> (proj_rows [g,H], proj_cols [g,W], sumsq [g,2]) as fp32."""
-    _need_cuda(masks=masks)
+    need_cuda(masks=masks)
     if masks.dim() != 3:
         raise RuntimeError(f'masks must be [g,H,W], got {tuple(masks.shape)}')
     g, H, W = masks.shape
@@ -135,11 +126,10 @@ def match_cost(cls, gt_labels, pred_proj, gt_proj, Q, counts, w_cls, w_dice, eps
         H, W = pp[0].shape[-1], pp[1].shape[-1]
         if gp[0].shape[-1] != H or gp[1].shape[-1] != W:
             raise RuntimeError(f'projections of {H}x{W} predictions and {gp[0].shape[-1]}x{gp[1].shape[-1]} ground truths')
-    ptr = lambda t: None if t is None else t.data_ptr()         # noqa: E731
     with torch.cuda.device(dev):
         _lib.check('bxi_match_cost_f32', _lib.load().bxi_match_cost_f32(
             ptr(cls), C, labels.data_ptr(), ptr(pp[0]), ptr(pp[1]), ptr(pp[2]), ptr(gp[0]), ptr(gp[1]), ptr(gp[2]), P, Q,
-            _lib.int_array(offsets), H, W, float(w_cls), float(w_dice), float(eps), cost.data_ptr(), status.data_ptr(), _stream(dev)))
+            _lib.int_array(offsets), H, W, float(w_cls), float(w_dice), float(eps), cost.data_ptr(), status.data_ptr(), current_stream(dev)))
     return cost[:total * Q], status
 
 
@@ -147,7 +137,7 @@ def linear_sum_assignment(cost, gt_labels, Q, counts):
     """Exact assignment of P problems in one launch.  ``cost`` as match_cost returns it (for one problem: a contiguous [Q, G] fp32
     matrix), ``gt_labels`` [sum(counts)] int64.  Returns (assigned_gt_inds [P,Q], assigned_labels [P,Q], pos_inds, pos_assigned_gt_inds,
     status [P]): the compacted arrays hold ``min(Q, counts[p])`` entries per problem, one problem after the other."""
-    _need_cuda(cost=cost, gt_labels=gt_labels)
+    need_cuda(cost=cost, gt_labels=gt_labels)
     offsets = _offsets(counts)
     P, total = len(counts), offsets[-1]
     dev = cost.device
@@ -164,7 +154,7 @@ def linear_sum_assignment(cost, gt_labels, Q, counts):
     with torch.cuda.device(dev):
         _lib.check('bxi_linear_sum_assignment_f32', _lib.load().bxi_linear_sum_assignment_f32(
             cost.data_ptr(), labels.data_ptr(), P, Q, _lib.int_array(offsets), gt_inds.data_ptr(), out_labels.data_ptr(), pos.data_ptr(),
-            pos_gt.data_ptr(), status.data_ptr(), _stream(dev)))
+            pos_gt.data_ptr(), status.data_ptr(), current_stream(dev)))
     return gt_inds, out_labels, pos, pos_gt, status
 
 
@@ -185,7 +175,7 @@ class ClassificationCost:
         self.weight = weight
 
     def __call__(self, cls_pred, gt_labels):
-        _need_cuda(cls_pred=cls_pred, gt_labels=gt_labels)
+        need_cuda(cls_pred=cls_pred, gt_labels=gt_labels)
         Q, G = cls_pred.shape[0], gt_labels.shape[0]
         if Q == 0 or G == 0:
             return cls_pred.new_zeros((Q, G), dtype=torch.float32)
@@ -211,7 +201,7 @@ class BoxMatchingCost:
         """``mask_preds`` [n,1,H,W] / [n,H,W] logits at the ground truths' size -- or at their own size with ``target_shape`` = (H, W),
         then sampled as ``F.interpolate(..., mode='bilinear', align_corners=False)`` would without being stored;  ``gt_box_masks``
         [g,1,H,W] / [g,H,W].  Returns the [n, g] cost."""
-        _need_cuda(mask_preds=mask_preds, gt_box_masks=gt_box_masks)
+        need_cuda(mask_preds=mask_preds, gt_box_masks=gt_box_masks)
         gt = _as_planes(gt_box_masks, 'gt_box_masks')
         n, g = mask_preds.shape[0], gt.shape[0]
         if n == 0 or g == 0:
@@ -265,9 +255,9 @@ class MaskHungarianAssigner:
         """All images of a batch: ``cls_scores`` [B,Q,C] or None, ``mask_preds`` [B,Q,h,w], per image ``gt_labels`` [G_i] and ``gt_masks``
         [G_i,H,W] (one H x W for the batch).  Returns (gt_inds [B,Q], labels [B,Q], pos_inds, pos_assigned_gt_inds, counts): launches only,
         nothing is read back.  ``last_status`` keeps the two device status words per image (cost: bad label, solver: non-finite cost)."""
-        _need_cuda(cls_scores=cls_scores, mask_preds=mask_preds)
-        _need_cuda(**{f'gt_labels_list[{i}]': t for i, t in enumerate(gt_labels_list)})
-        _need_cuda(**{f'gt_masks_list[{i}]': t for i, t in enumerate(gt_masks_list)})
+        need_cuda(cls_scores=cls_scores, mask_preds=mask_preds)
+        need_cuda(**{f'gt_labels_list[{i}]': t for i, t in enumerate(gt_labels_list)})
+        need_cuda(**{f'gt_masks_list[{i}]': t for i, t in enumerate(gt_masks_list)})
         B, Q = mask_preds.shape[:2]
         if len(gt_labels_list) != B or len(gt_masks_list) != B:
             raise RuntimeError(f'{B} images but {len(gt_labels_list)} label and {len(gt_masks_list)} mask entries')
@@ -302,7 +292,7 @@ class MaskHungarianAssigner:
         with ``target_shape`` (nothing is up-sampled in memory then).  Returns an AssignResult: ``gt_inds`` 0 background / g + 1,
         ``labels`` -1 or the matched label, ``max_overlaps`` None."""
         assert gt_bboxes_ignore is None, 'Only case when gt_bboxes_ignore is None is supported.'
-        _need_cuda(cls_pred=cls_pred, mask_pred=mask_pred, gt_labels=gt_labels, gt_mask=gt_mask)
+        need_cuda(cls_pred=cls_pred, mask_pred=mask_pred, gt_labels=gt_labels, gt_mask=gt_mask)
         num_gt, num_query = gt_labels.shape[0], mask_pred.shape[0]
         if num_query == 0:
             empty = mask_pred.new_full((0,), -1, dtype=torch.long)
@@ -321,7 +311,7 @@ def box2mask_get_targets(cls_scores, mask_preds, gt_labels_list, gt_masks_list, 
     no ``.item()``, nothing of size Q*H*W.  Returns (labels_list, label_weights_list, mask_targets_list, mask_weights_list,
     num_total_pos, num_total_neg), the two totals Python ints from ``min(Q, G_i)``.  An image whose cost is not finite (the assigner's
     ``last_status``) comes back all background, and its ``mask_targets`` rows are those of its first ground truth."""
-    _need_cuda(cls_scores=cls_scores, mask_preds=mask_preds)
+    need_cuda(cls_scores=cls_scores, mask_preds=mask_preds)
     B, Q = mask_preds.shape[:2]
     gt_inds, assigned, _, pos_gt, counts = assigner.assign_batch(cls_scores, mask_preds, gt_labels_list, gt_masks_list)
     labels_list, label_weights_list, mask_targets_list, mask_weights_list = [], [], [], []

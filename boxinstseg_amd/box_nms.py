@@ -23,6 +23,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._common import cfg_get, current_stream, need_cuda, ptr
 
 __all__ = ['nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes', 'location_scores', 'det_candidates', 'box_nms', 'det_gather',
            'SORT_MAX', 'NMS_ROUND', 'KEEP_TILE']
@@ -30,41 +31,21 @@ __all__ = ['nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes', 'loca
 SORT_MAX, NMS_ROUND, KEEP_TILE = _lib.DET_SORT_MAX, _lib.DET_NMS_ROUND, _lib.DET_KEEP_TILE
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
-
-
-def _get(cfg, name, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(name, default)
-    return getattr(cfg, name, default)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def parse_test_cfg(cfg):
     """``test_cfg`` (dict or namespace) -> dict(nms_pre, score_thr, iou_threshold, max_per_img, class_agnostic, nms_max_num)."""
-    nms_cfg = _get(cfg, 'nms')
+    nms_cfg = cfg_get(cfg, 'nms')
     if nms_cfg is None:
         raise TypeError('test_cfg has no `nms` entry')
-    kind = _get(nms_cfg, 'type', 'nms')
+    kind = cfg_get(nms_cfg, 'type', 'nms')
     if kind != 'nms':
         raise NotImplementedError(f"nms type {kind!r} is not supported: only dict(type='nms', iou_threshold=...)")
-    score_thr = _get(cfg, 'score_thr')
+    score_thr = cfg_get(cfg, 'score_thr')
     if score_thr is None:
         raise TypeError('test_cfg has no `score_thr`')
-    max_per_img = _get(cfg, 'max_per_img', -1)
-    return dict(nms_pre=int(_get(cfg, 'nms_pre', -1)), score_thr=float(score_thr), iou_threshold=float(_get(nms_cfg, 'iou_threshold')),
-                max_per_img=int(-1 if max_per_img is None else max_per_img), class_agnostic=bool(_get(nms_cfg, 'class_agnostic', False)),
-                nms_max_num=int(_get(nms_cfg, 'max_num', -1)))
+    max_per_img = cfg_get(cfg, 'max_per_img', -1)
+    return dict(nms_pre=int(cfg_get(cfg, 'nms_pre', -1)), score_thr=float(score_thr), iou_threshold=float(cfg_get(nms_cfg, 'iou_threshold')),
+                max_per_img=int(-1 if max_per_img is None else max_per_img), class_agnostic=bool(cfg_get(nms_cfg, 'class_agnostic', False)),
+                nms_max_num=int(cfg_get(nms_cfg, 'max_num', -1)))
 
 
 # ---- the four entry points ------------------------------------------------------------------------------------------------
@@ -76,7 +57,7 @@ class _Levels:
         if not (1 <= n <= _lib.DET_MAX_LEVELS) or len(bbox_preds) != n or len(centernesses) != n or len(strides) != n or \
                 (param_preds is not None and len(param_preds) != n):
             raise RuntimeError(f'1..{_lib.DET_MAX_LEVELS} levels with cls, bbox, centerness (and params) and a stride each, got {n}')
-        _need_cuda(**{f'cls_scores[{i}]': t for i, t in enumerate(cls_scores)}, **{f'bbox_preds[{i}]': t for i, t in enumerate(bbox_preds)},
+        need_cuda(**{f'cls_scores[{i}]': t for i, t in enumerate(cls_scores)}, **{f'bbox_preds[{i}]': t for i, t in enumerate(bbox_preds)},
                    **{f'centernesses[{i}]': t for i, t in enumerate(centernesses)},
                    **({} if param_preds is None else {f'param_preds[{i}]': t for i, t in enumerate(param_preds)}))
         f = lambda t: t.detach().to(torch.float32).contiguous()            # noqa: E731
@@ -106,7 +87,7 @@ def location_scores(levels: _Levels) -> torch.Tensor:
     out = torch.empty((levels.B, levels.M_all), dtype=torch.float32, device=levels.dev)
     with torch.cuda.device(levels.dev):
         _lib.check('bxi_det_location_score_f32', _lib.load().bxi_det_location_score_f32(
-            levels.arr, levels.n, levels.B, levels.C, out.data_ptr(), _stream(levels.dev)))
+            levels.arr, levels.n, levels.B, levels.C, out.data_ptr(), current_stream(levels.dev)))
     return out
 
 
@@ -117,7 +98,7 @@ def det_candidates(levels: _Levels, sel, img_dims, rescale, score_thr, cap, fill
     B, dev = levels.B, levels.dev
     M = levels.M_all if sel is None else int(sel.shape[1])
     if sel is not None:
-        _need_cuda(sel=sel)
+        need_cuda(sel=sel)
         if sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous():
             raise RuntimeError(f'sel must be contiguous int64 [{B}, M], got {sel.dtype} {tuple(sel.shape)}')
     rows = max(cap, 1)
@@ -133,8 +114,8 @@ def det_candidates(levels: _Levels, sel, img_dims, rescale, score_thr, cap, fill
     dims = _lib.float_array([v for row in img_dims for v in row])
     with torch.cuda.device(dev):
         _lib.check('bxi_det_candidates_f32', lib.bxi_det_candidates_f32(
-            levels.arr, levels.n, B, levels.C, _ptr(sel), M, dims, 1 if rescale else 0, float(score_thr), int(cap), boxes.data_ptr(),
-            scores.data_ptr(), labels.data_ptr(), pos.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)))
+            levels.arr, levels.n, B, levels.C, ptr(sel), M, dims, 1 if rescale else 0, float(score_thr), int(cap), boxes.data_ptr(),
+            scores.data_ptr(), labels.data_ptr(), pos.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel() * 4, current_stream(dev)))
     return boxes, scores, labels, pos, count
 
 
@@ -142,7 +123,7 @@ def box_nms(boxes, scores, labels, count, iou_threshold, offset=0, max_num=-1, o
     """Greedy NMS of P segments: ``boxes`` [P,cap,4], ``scores`` [P,cap], ``labels`` [P,cap] int64 or None (class-agnostic), ``count`` [P]
     int32 on the device, ``order`` [P,cap] int32 or None (the library sorts; needs count <= SORT_MAX).  Returns (keep [P,max_keep] int32,
     n_keep [P] int32, status [P] int32), all on the device; max_keep = max_num when max_num > 0, else cap (the rule of the header)."""
-    _need_cuda(boxes=boxes, scores=scores, labels=labels, count=count, order=order)
+    need_cuda(boxes=boxes, scores=scores, labels=labels, count=count, order=order)
     if boxes.dim() != 3 or boxes.shape[-1] != 4 or boxes.dtype != torch.float32 or not boxes.is_contiguous():
         raise RuntimeError(f'boxes must be contiguous fp32 [P,cap,4], got {boxes.dtype} {tuple(boxes.shape)}')
     P, cap = int(boxes.shape[0]), int(boxes.shape[1])
@@ -165,8 +146,8 @@ def box_nms(boxes, scores, labels, count, iou_threshold, offset=0, max_num=-1, o
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         _lib.check('bxi_box_nms_f32', lib.bxi_box_nms_f32(
-            boxes.data_ptr(), scores.data_ptr(), _ptr(labels), count.data_ptr(), _ptr(order), P, cap, float(iou_threshold), int(offset),
-            int(max_num), keep.data_ptr(), n_keep.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)))
+            boxes.data_ptr(), scores.data_ptr(), ptr(labels), count.data_ptr(), ptr(order), P, cap, float(iou_threshold), int(offset),
+            int(max_num), keep.data_ptr(), n_keep.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel() * 4, current_stream(dev)))
     return keep, n_keep, status
 
 
@@ -184,9 +165,9 @@ def det_gather(levels: _Levels, sel, cand, keep, n_keep):
     det_level_inds = torch.empty((B, max_keep), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _lib.check('bxi_det_gather_f32', _lib.load().bxi_det_gather_f32(
-            levels.arr, levels.n, B, levels.C, P, _ptr(sel), M, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), pos.data_ptr(), cap,
+            levels.arr, levels.n, B, levels.C, P, ptr(sel), M, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), pos.data_ptr(), cap,
             keep.data_ptr(), n_keep.data_ptr(), max_keep, dets.data_ptr(), det_labels.data_ptr(), det_params.data_ptr() if P else None,
-            det_coors.data_ptr(), det_level_inds.data_ptr(), _stream(dev)))
+            det_coors.data_ptr(), det_level_inds.data_ptr(), current_stream(dev)))
     return dets, det_labels, det_params, det_coors, det_level_inds
 
 
@@ -215,7 +196,7 @@ def _nms_single(boxes, scores, labels, iou_threshold, offset, max_num):
 
 def nms(boxes, scores, iou_threshold, offset=0, score_threshold=0, max_num=-1):
     """``mmcv.ops.nms.nms``: ``boxes`` [n,4], ``scores`` [n] on the GPU -> (dets [k,5], inds [k] int64), in descending score order."""
-    _need_cuda(boxes=boxes, scores=scores)
+    need_cuda(boxes=boxes, scores=scores)
     assert boxes.dim() == 2 and boxes.size(1) == 4 and boxes.size(0) == scores.size(0)
     assert offset in (0, 1)
     src = None
@@ -231,7 +212,7 @@ def batched_nms(boxes, scores, idxs, nms_cfg, class_agnostic=False):
     """``mmcv.ops.nms.batched_nms``: NMS among boxes of the same ``idxs`` -> (dets [k,5], keep [k]).  ``nms_cfg`` keys: ``type`` ('nms'
     only), ``iou_threshold``, ``class_agnostic``, ``max_num``; ``split_thr`` is accepted and ignored (mmcv's threshold above which it
     loops over the classes; the result is the same).  Any other key raises."""
-    _need_cuda(boxes=boxes, scores=scores, idxs=idxs)
+    need_cuda(boxes=boxes, scores=scores, idxs=idxs)
     cfg = dict(nms_cfg)
     class_agnostic = cfg.pop('class_agnostic', class_agnostic)
     kind = cfg.pop('type', 'nms')
@@ -251,7 +232,7 @@ def nms_with_others(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, 
     the background column last.  A (row, class) pair is a candidate where its class score is above ``score_thr``; its score is the class
     score times the row's ``score_factors``.  Returns (dets [k,5], labels [k], the rows of every ``others`` item that belong to the kept
     detections); the labels are on the boxes' device (the reference leaves them on the CPU)."""
-    _need_cuda(multi_bboxes=multi_bboxes, multi_scores=multi_scores, score_factors=score_factors)
+    need_cuda(multi_bboxes=multi_bboxes, multi_scores=multi_scores, score_factors=score_factors)
     n, C = multi_scores.size(0), multi_scores.size(1) - 1
     if others is not None and any(item.size(0) != n for item in others):
         raise RuntimeError(f'every item of `others` needs {n} rows')

@@ -26,7 +26,6 @@ constexpr int kChunk = BXI_FCOS_GT_CHUNK;
 constexpr float kInf = 1e8f;                 // condinst_head.py:16
 
 struct Ranges { float lo[kMaxL], hi[kMaxL], radius[kMaxL]; };   // radius = (float)(stride * center_sample_radius)
-struct GtOffsets { int v[BXI_MAX_IMAGES + 1]; };
 struct Maps {
     const float* cls[kMaxL]; const float* bbox[kMaxL]; const float* ctr[kMaxL];
     float* gcls[kMaxL]; float* gbbox[kMaxL]; float* gctr[kMaxL];
@@ -196,43 +195,7 @@ __global__ __launch_bounds__(256) void fcos_focal_kernel(Maps m, LocGrid g, Flat
     float* __restrict__ dst = m.gcls[l];
     const float denom = fmaxf(norm[0], 1.f) + FLT_EPSILON;
     const float scale = lw / denom;
-    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && e0 + 3 < count;
-    float v[4] = {0.f, 0.f, 0.f, 0.f}, gr[4];
-    if (vec) {
-        const float4 q = *reinterpret_cast<const float4*>(src + e0);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e0 + j < count) v[j] = src[e0 + j];
-    }
-    // element e of the level is (b, c, yx) = (e / (C hw), (e / hw) % C, e % hw); its label is row B first_l + b hw + yx
-    int plane = e0 / hw, yx = e0 - plane * hw;
-    int b = plane / C, c = plane - b * C;
-    const size_t row0 = (size_t)g.B * g.first[l];
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float lo = 0.f;
-        gr[j] = 0.f;
-        if (e0 + j < count) {
-            const bool t = labels[row0 + (size_t)b * hw + yx] == (int64_t)c;
-            focal_one<G2>(v[j], t, gamma, alpha, scale, lo, gr[j]);
-        }
-        sum += lo;
-        if (++yx == hw) {
-            yx = 0;
-            if (++c == C) { c = 0; ++b; }
-        }
-    }
-    if (vec) {
-        *reinterpret_cast<float4*>(dst + e0) = make_float4(gr[0], gr[1], gr[2], gr[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e0 + j < count) dst[e0 + j] = gr[j];
-    }
-    const double tot = block_sum_f64((double)sum, s4d);
+    const double tot = focal_tile<G2>(src, dst, count, e0, hw, C, (size_t)g.B * g.first[l], labels, gamma, alpha, scale, s4d);
     if (tid == 0) {
         int32_t* p = partials + 4 * (size_t)(part_first + blk);
         p[0] = __float_as_int((float)(tot * (double)scale));
@@ -387,11 +350,7 @@ extern "C" int bxi_fcos_targets_f32(const bxi_fcos_level* levels_host, int n_lev
     if (B == 0) return BXI_OK;
     if (!regress_ranges_host || !gt_offsets_host) return BXI_ERR_NULL_POINTER;
     GtOffsets off;
-    if (gt_offsets_host[0] != 0) return BXI_ERR_BAD_SHAPE;
-    for (int b = 0; b <= BXI_MAX_IMAGES; ++b) {
-        off.v[b] = gt_offsets_host[b <= B ? b : B];
-        if (b > 0 && off.v[b] < off.v[b - 1]) return BXI_ERR_BAD_SHAPE;
-    }
+    if (int rc = read_offsets(gt_offsets_host, B, off)) return rc;
     if (!fits_i32((int64_t)off.v[B] * 4)) return BXI_ERR_BAD_SHAPE;
     Ranges rg;
     if (center_sampling && !(center_sample_radius >= 0.0)) return BXI_ERR_BAD_ARGUMENT;

@@ -1,6 +1,7 @@
 // focal_device.hpp -- what the two training-loss files share (fcos_loss.hip, solo_targets.hip): the (level, image, tile) grid of the
 // flattened training order, the flat segment grid, the fixed-order workgroup sums, the sigmoid focal loss of one logit with its
-// derivative, and the flat rescale kernel of the backward step.  Everything sits in an unnamed namespace: each file has its own copy.
+// derivative and of one workgroup's tile of a [B][C][HW] map, the flat rescale kernel of the backward step, and the per-image box
+// offsets as the kernels take them.  Everything sits in an unnamed namespace: each file has its own copy.
 #pragma once
 
 #include <float.h>
@@ -39,6 +40,8 @@ struct FlatGrid {
     int blk_first[3 * kMaxL + 1];
     int n;                          // segments
 };
+// first box of every image, padded with the total: v[b] = gt_offsets_host[min(b, B)]
+struct GtOffsets { int v[BXI_MAX_IMAGES + 1]; };
 
 // workgroup sums in a fixed order: the DPP wave total, then the four waves pairwise (thread 0 holds the result)
 __device__ __forceinline__ double block_sum_f64(double v, double* s4) {
@@ -79,6 +82,51 @@ __device__ __forceinline__ void focal_one(float x, bool t, float gamma, float al
     const float dpt = t ? -(p * q) : p * q;
     loss = aw * bce * mod;
     grad = scale * aw * ((t ? -q : p) * mod + bce * dmod * dpt);           // d bce / dx = sigmoid(x) - t
+}
+
+// One workgroup's tile of a flat [B][C][hw] map: four consecutive elements per thread from e0 (one 16-byte load and store where
+// the pointers allow it, four scalar ones elsewhere and on the tail -- the same element-to-thread map either way, so the sums do not
+// depend on alignment).  Writes the four gradients and returns the workgroup's loss total before `scale` (thread 0 holds it).
+template <bool G2>
+__device__ __forceinline__ double focal_tile(const float* __restrict__ src, float* __restrict__ dst, int count, int e0, int hw, int C,
+                                             size_t row0, const int64_t* __restrict__ labels, float gamma, float alpha, float scale,
+                                             double* s4d) {
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && e0 + 3 < count;
+    float v[4] = {0.f, 0.f, 0.f, 0.f}, gr[4];
+    if (vec) {
+        const float4 q = *reinterpret_cast<const float4*>(src + e0);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (e0 + j < count) v[j] = src[e0 + j];
+    }
+    // element e of the level is (b, c, yx) = (e / (C hw), (e / hw) % C, e % hw); its label is row row0 + b hw + yx
+    int plane = e0 / hw, yx = e0 - plane * hw;
+    int b = plane / C, c = plane - b * C;
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        float lo = 0.f;
+        gr[j] = 0.f;
+        if (e0 + j < count) {
+            const bool t = labels[row0 + (size_t)b * hw + yx] == (int64_t)c;
+            focal_one<G2>(v[j], t, gamma, alpha, scale, lo, gr[j]);
+        }
+        sum += lo;
+        if (++yx == hw) {
+            yx = 0;
+            if (++c == C) { c = 0; ++b; }
+        }
+    }
+    if (vec) {
+        *reinterpret_cast<float4*>(dst + e0) = make_float4(gr[0], gr[1], gr[2], gr[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (e0 + j < count) dst[e0 + j] = gr[j];
+    }
+    return block_sum_f64((double)sum, s4d);
 }
 
 // ---- backward rescale -----------------------------------------------------------------------------------------------------
@@ -154,6 +202,18 @@ int64_t make_flat(const LocGrid& g, const int* chan, int per_level, FlatGrid& f)
     f.blk_first[3 * kMaxL] = (int)blk;
     for (int s = f.n; s <= 3 * kMaxL; ++s) f.blk_first[s] = (int)blk;
     return blk;
+}
+
+int read_offsets(const int* gt_offsets_host, int B, GtOffsets& off) {
+    if (B < 0 || B > BXI_MAX_IMAGES) return BXI_ERR_BAD_SHAPE;
+    if (B == 0) return BXI_OK;
+    if (!gt_offsets_host) return BXI_ERR_NULL_POINTER;
+    if (gt_offsets_host[0] != 0) return BXI_ERR_BAD_SHAPE;
+    for (int b = 0; b <= BXI_MAX_IMAGES; ++b) {
+        off.v[b] = gt_offsets_host[b <= B ? b : B];
+        if (b > 0 && off.v[b] < off.v[b - 1]) return BXI_ERR_BAD_SHAPE;
+    }
+    return BXI_OK;
 }
 
 bool workspace_ok(const void* ws, size_t have, size_t need) { return ws && have >= need && !(reinterpret_cast<uintptr_t>(ws) & 3); }

@@ -39,7 +39,6 @@ struct MaskOuts {
     int f[kMaxF], h[kMaxF], w[kMaxF];
     int n, band, nb;                        // factors, source rows per band, bands per instance
 };
-struct GtOffsets { int v[BXI_MAX_IMAGES + 1]; };
 
 // ---- mask pass ------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void add_byte(unsigned v, int x, int y, unsigned& m00, unsigned long long& m10, unsigned long long& m01) {
@@ -292,43 +291,7 @@ __global__ __launch_bounds__(256) void solo_cate_focal_kernel(CateMaps m, LocGri
     float* __restrict__ dst = m.gcls[l];
     const float denom = (float)(num_ins[0] + 1) + FLT_EPSILON;          // avg_factor = num_ins + 1, then weight_reduce_loss's eps
     const float scale = lw / denom;
-    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && e0 + 3 < count;
-    float v[4] = {0.f, 0.f, 0.f, 0.f}, gr[4];
-    if (vec) {
-        const float4 q = *reinterpret_cast<const float4*>(src + e0);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e0 + j < count) v[j] = src[e0 + j];
-    }
-    // element e of the level is (b, c, yx) = (e / (C hw), (e / hw) % C, e % hw); its label is row B first_l + b hw + yx
-    int plane = e0 / hw, yx = e0 - plane * hw;
-    int b = plane / C, c = plane - b * C;
-    const size_t row0 = (size_t)g.B * g.first[l];
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float lo = 0.f;
-        gr[j] = 0.f;
-        if (e0 + j < count) {
-            const bool t = labels[row0 + (size_t)b * hw + yx] == (int64_t)c;
-            focal_one<G2>(v[j], t, gamma, alpha, scale, lo, gr[j]);
-        }
-        sum += lo;
-        if (++yx == hw) {
-            yx = 0;
-            if (++c == C) { c = 0; ++b; }
-        }
-    }
-    if (vec) {
-        *reinterpret_cast<float4*>(dst + e0) = make_float4(gr[0], gr[1], gr[2], gr[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e0 + j < count) dst[e0 + j] = gr[j];
-    }
-    const double tot = block_sum_f64((double)sum, s4d);
+    const double tot = focal_tile<G2>(src, dst, count, e0, hw, C, (size_t)g.B * g.first[l], labels, gamma, alpha, scale, s4d);
     if (tid == 0) {                                         // the partial stays fp64 (two words: the workspace is 4-byte aligned)
         const long long bits = __double_as_longlong(tot * (double)scale);
         partials[2 * (size_t)blk] = (int32_t)bits;
@@ -346,18 +309,6 @@ __global__ __launch_bounds__(256) void solo_cate_finish_kernel(const int32_t* __
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-int read_offsets(const int* gt_offsets_host, int B, GtOffsets& off) {
-    if (B < 0 || B > BXI_MAX_IMAGES) return BXI_ERR_BAD_SHAPE;
-    if (B == 0) return BXI_OK;
-    if (!gt_offsets_host) return BXI_ERR_NULL_POINTER;
-    if (gt_offsets_host[0] != 0) return BXI_ERR_BAD_SHAPE;
-    for (int b = 0; b <= BXI_MAX_IMAGES; ++b) {
-        off.v[b] = gt_offsets_host[b <= B ? b : B];
-        if (b > 0 && off.v[b] < off.v[b - 1]) return BXI_ERR_BAD_SHAPE;
-    }
-    return BXI_OK;
-}
-
 int cate_grid(const int* num_grids_host, int n_levels, int B, int C, LocGrid& g, FlatGrid& f, int64_t& blocks) {
     if (n_levels < 1 || n_levels > kMaxL || C < 1) return BXI_ERR_BAD_SHAPE;
     if (!num_grids_host) return BXI_ERR_NULL_POINTER;

@@ -9,16 +9,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
+from ._common import current_stream, need_cuda
 
 
 def _target_arg(t: torch.Tensor):
@@ -31,21 +22,21 @@ def _target_arg(t: torch.Tensor):
 def meanfield_kernel(feature_map: torch.Tensor, kernel_size: int = 3, alpha0: float = 3.0, theta0: float = 0.5,
                      theta1: float = 30.0) -> torch.Tensor:
     """``feature_map`` [B,C,H,W] -> neighbourhood kernel [B,k*k,H,W] (``MeanField.__init__`` :597-611)."""
-    _need_cuda(feature_map=feature_map)
+    need_cuda(feature_map=feature_map)
     f = feature_map.detach().to(torch.float32).contiguous()
     B, Cc, H, W = f.shape
     out = torch.empty((B, kernel_size * kernel_size, H, W), dtype=torch.float32, device=f.device)
     with torch.cuda.device(f.device):
         _lib.check('bxi_meanfield_kernel_f32', _lib.load().bxi_meanfield_kernel_f32(
             f.data_ptr(), B, Cc, H, W, int(kernel_size), float(alpha0), float(theta0), float(theta1), out.data_ptr(),
-            _stream(f.device)))
+            current_stream(f.device)))
     return out
 
 
 def meanfield_forward(kernel: torch.Tensor, x: torch.Tensor, targets: torch.Tensor, iters: int, base: float,
                       img_inds: torch.Tensor = None, inter_img_mask: torch.Tensor = None, gamma: float = 0.01):
     """Batched ``MeanField.forward``: kernel [B,k*k,H,W], x / targets [N,(1,)H,W], img_inds [N] -> (ret like x, valid [N])."""
-    _need_cuda(kernel=kernel, x=x, targets=targets, img_inds=img_inds, inter_img_mask=inter_img_mask)
+    need_cuda(kernel=kernel, x=x, targets=targets, img_inds=img_inds, inter_img_mask=inter_img_mask)
     dev = x.device
     B, K2, H, W = kernel.shape
     ks = int(round(K2 ** 0.5))
@@ -70,7 +61,7 @@ def meanfield_forward(kernel: torch.Tensor, x: torch.Tensor, targets: torch.Tens
         _lib.check('bxi_meanfield_forward_f32', lib.bxi_meanfield_forward_f32(
             kc.data_ptr(), B, H, W, ks, xc.data_ptr(), tc.data_ptr(), t_u8, 0 if img is None else img.data_ptr(), N,
             int(iters), float(base), 0 if inter is None else inter.data_ptr(), float(gamma), ret.data_ptr(),
-            valid.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+            valid.data_ptr(), ws.data_ptr(), ws.numel(), current_stream(dev)))
     return ret.view(shape), valid
 
 
@@ -108,7 +99,7 @@ class MeanField(torch.nn.Module):
 class _DiceLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target):
-        _need_cuda(input=inp, target=target)
+        need_cuda(input=inp, target=target)
         dev = inp.device
         N = inp.size(0)
         L = 1
@@ -122,7 +113,7 @@ class _DiceLoss(torch.autograd.Function):
         sums = torch.empty((max(N, 1), 2), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check('bxi_dice_loss_forward_f32', _lib.load().bxi_dice_loss_forward_f32(
-                ic.data_ptr(), tc.data_ptr(), t_u8, N, max(L, 1), loss.data_ptr(), sums.data_ptr(), _stream(dev)))
+                ic.data_ptr(), tc.data_ptr(), t_u8, N, max(L, 1), loss.data_ptr(), sums.data_ptr(), current_stream(dev)))
         ctx.save_for_backward(ic, tc, sums)
         ctx.meta = (t_u8, inp.shape, inp.dtype)
         return loss
@@ -138,7 +129,7 @@ class _DiceLoss(torch.autograd.Function):
         with torch.cuda.device(ic.device):
             _lib.check('bxi_dice_loss_backward_f32', _lib.load().bxi_dice_loss_backward_f32(
                 ic.data_ptr(), tc.data_ptr(), t_u8, N, max(L, 1), sums.data_ptr(), g.data_ptr(), gi.data_ptr(),
-                _stream(ic.device)))
+                current_stream(ic.device)))
         return gi.view(shape).to(dtype), None
 
 
@@ -150,7 +141,7 @@ def dice_loss(input, target):
 class _MilLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inp, target):
-        _need_cuda(input=inp, target=target)
+        need_cuda(input=inp, target=target)
         if inp.dim() != 3:
             raise RuntimeError('mil_loss expects input [N,H,W]')
         dev = inp.device
@@ -164,7 +155,7 @@ class _MilLoss(torch.autograd.Function):
         state = torch.empty(max(lib.bxi_mil_loss_state_bytes(N, H, W), 16), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             _lib.check('bxi_mil_loss_forward_f32', lib.bxi_mil_loss_forward_f32(
-                ic.data_ptr(), tc.data_ptr(), t_u8, N, H, W, loss.data_ptr(), state.data_ptr(), _stream(dev)))
+                ic.data_ptr(), tc.data_ptr(), t_u8, N, H, W, loss.data_ptr(), state.data_ptr(), current_stream(dev)))
         ctx.save_for_backward(state)
         ctx.meta = (N, H, W, inp.dtype)
         return loss
@@ -178,7 +169,7 @@ class _MilLoss(torch.autograd.Function):
         gi = torch.empty((N, H, W), dtype=torch.float32, device=state.device)
         with torch.cuda.device(state.device):
             _lib.check('bxi_mil_loss_backward_f32', _lib.load().bxi_mil_loss_backward_f32(
-                N, H, W, state.data_ptr(), g.data_ptr(), gi.data_ptr(), _stream(state.device)))
+                N, H, W, state.data_ptr(), g.data_ptr(), gi.data_ptr(), current_stream(state.device)))
         return gi.to(dtype), None
 
 

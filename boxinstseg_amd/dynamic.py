@@ -9,10 +9,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+from ._common import current_stream
 
 
 class DynamicMaskHead(torch.autograd.Function):
@@ -40,7 +37,7 @@ class DynamicMaskHead(torch.autograd.Function):
             _lib.check('bxi_dynamic_mask_forward_f32', _lib.load().bxi_dynamic_mask_forward_f32(
                 feat_c.data_ptr(), B, C, H, W, params_c.data_ptr(), N, coors_c.data_ptr(), lvl.data_ptr(),
                 img.data_ptr(), soi.data_ptr(), soi.numel(), int(in_stride), int(factor), int(bool(disable_rel_coors)),
-                out.data_ptr(), _stream(dev)))
+                out.data_ptr(), current_stream(dev)))
         ctx.save_for_backward(feat_c, params_c, coors_c, lvl, img, soi)
         ctx.cfg = (int(in_stride), int(factor), int(bool(disable_rel_coors)))
         ctx.dtypes = (feat.dtype, params.dtype)
@@ -64,7 +61,7 @@ class DynamicMaskHead(torch.autograd.Function):
             _lib.check('bxi_dynamic_mask_backward_f32', lib.bxi_dynamic_mask_backward_f32(
                 feat.data_ptr(), B, C, H, W, params.data_ptr(), N, coors.data_ptr(), lvl.data_ptr(), img.data_ptr(),
                 soi.data_ptr(), soi.numel(), in_stride, factor, no_rel, g.data_ptr(), g_feat.data_ptr(),
-                g_params.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+                g_params.data_ptr(), ws.data_ptr(), ws.numel(), current_stream(dev)))
         return (g_feat.to(ctx.dtypes[0]), g_params.to(ctx.dtypes[1]), None, None, None, None, None, None, None)
 
 
@@ -105,7 +102,7 @@ class GenericDynamicMaskHead(torch.autograd.Function):
             _lib.check('bxi_dynamic_mask_generic_forward_f32', _lib.load().bxi_dynamic_mask_generic_forward_f32(
                 feat_c.data_ptr(), B, C, H, W, params_c.data_ptr(), N, int(layers), int(channels), coors_c.data_ptr(), lvl.data_ptr(),
                 img.data_ptr(), soi.data_ptr(), soi.numel(), int(in_stride), int(factor), int(bool(disable_rel_coors)),
-                out.data_ptr(), _stream(dev)))
+                out.data_ptr(), current_stream(dev)))
         ctx.save_for_backward(feat_c, params_c, coors_c, lvl, img, soi)
         ctx.cfg = (int(in_stride), int(factor), int(bool(disable_rel_coors)), int(layers), int(channels))
         ctx.dtypes = (feat.dtype, params.dtype)
@@ -129,7 +126,7 @@ class GenericDynamicMaskHead(torch.autograd.Function):
             _lib.check('bxi_dynamic_mask_generic_backward_f32', lib.bxi_dynamic_mask_generic_backward_f32(
                 feat.data_ptr(), B, C, H, W, params.data_ptr(), N, layers, channels, coors.data_ptr(), lvl.data_ptr(), img.data_ptr(),
                 soi.data_ptr(), soi.numel(), in_stride, factor, no_rel, g.data_ptr(), g_feat.data_ptr(), g_params.data_ptr(),
-                ws.data_ptr(), ws.numel(), _stream(dev)))
+                ws.data_ptr(), ws.numel(), current_stream(dev)))
         return (g_feat.to(ctx.dtypes[0]), g_params.to(ctx.dtypes[1])) + (None,) * 9
 
 
@@ -221,7 +218,7 @@ def _paste(logits, img_inds, offsets, dims, total, out_stride, threshold):
     with torch.cuda.device(dev):
         _lib.check('bxi_mask_paste_u8', _lib.load().bxi_mask_paste_u8(
             lg.data_ptr(), N, h, w, int(out_stride), img.data_ptr(), off.data_ptr(), len(dims), dims_host, float(threshold),
-            masks.data_ptr(), _stream(dev)))
+            masks.data_ptr(), current_stream(dev)))
     return masks
 
 

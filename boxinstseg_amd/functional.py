@@ -22,26 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-
-
-def _require_cuda(**tensors: Optional[torch.Tensor]) -> None:
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
-
-
-_RAW_STREAM = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-
-
-def _current_stream(dev: torch.device) -> int:
-    """The current stream's handle (the raw getter skips building a Stream object: 0.3 instead of 1.9 us)."""
-    if _RAW_STREAM is not None:
-        return _RAW_STREAM(dev.index if dev.index is not None else torch.cuda.current_device())
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _stream(device: torch.device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+from ._common import current_stream, need_cuda
 
 
 def rows_removed(bottom_pixels_removed: int, img_shape: Sequence[int], ori_shape: Sequence[int]) -> int:
@@ -135,7 +116,7 @@ def color_affinity(imgs: torch.Tensor, img_metas: Sequence[dict], *, out_stride:
                    image_masks: Optional[torch.Tensor] = None, denormalize: bool = True
                    ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor], torch.Tensor]:
     """-> (sim [B,K,h,w] f32 | None, bits [B,h,w] u8/int32 | None, lab [B,3,h,w] f32)."""
-    _require_cuda(imgs=imgs, image_masks=image_masks)
+    need_cuda(imgs=imgs, image_masks=image_masks)
     batch = _Batch(imgs, img_metas, bottom_pixels_removed, image_masks, denormalize)
     B, Hc, Wc = batch.B, batch.Hc, batch.Wc
     if Hc % out_stride or Wc % out_stride:
@@ -152,7 +133,7 @@ def color_affinity(imgs: torch.Tensor, img_metas: Sequence[dict], *, out_stride:
         _lib.check('bxi_color_affinity_f32', _lib.load().bxi_color_affinity_f32(
             C.byref(batch.struct), int(out_stride), int(pairwise_size), int(pairwise_dilation),
             float(pairwise_color_thresh), lab.data_ptr(), 0, 0 if sim is None else sim.data_ptr(),
-            0 if bits is None else bits.data_ptr(), _stream(dev)))
+            0 if bits is None else bits.data_ptr(), current_stream(dev)))
     return sim, bits, lab
 
 
@@ -160,7 +141,7 @@ def box_bitmasks(gt_bboxes: Sequence[torch.Tensor], Hc: int, Wc: int, stride: in
     """Per-box {0,1} masks sampled at ``[start::stride, start::stride]`` -> [G, ., .] f32 (:1426-1432)."""
     if not gt_bboxes:
         raise RuntimeError('gt_bboxes is empty')
-    _require_cuda(**{f'gt_bboxes[{i}]': b for i, b in enumerate(gt_bboxes)})
+    need_cuda(**{f'gt_bboxes[{i}]': b for i, b in enumerate(gt_bboxes)})
     dev = gt_bboxes[0].device
     boxes = [b.detach().to(torch.float32).contiguous().view(-1, 4) for b in gt_bboxes]
     ptrs = _lib.ptr_array(b.data_ptr() if b.numel() else 0 for b in boxes)
@@ -171,7 +152,7 @@ def box_bitmasks(gt_bboxes: Sequence[torch.Tensor], Hc: int, Wc: int, stride: in
     with torch.cuda.device(dev):
         _lib.check('bxi_box_bitmasks_f32', _lib.load().bxi_box_bitmasks_f32(
             C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(cnt, C.POINTER(C.c_int)), len(boxes), int(Hc), int(Wc),
-            int(stride), int(start), out.data_ptr(), _stream(dev)))
+            int(stride), int(start), out.data_ptr(), current_stream(dev)))
     return out
 
 
@@ -318,7 +299,7 @@ def prepare_targets(imgs: torch.Tensor, img_metas: Sequence[dict], gt_bboxes: Se
     = the current stream), it takes image -> Lab -> colour predicates -> pair counts off the loss's critical path; hand the result to
     :func:`boxinst_mask_loss` (``targets=``).  Returns ``None`` where the library does not build it (more than 1024 GT boxes, a
     threshold <= 0, another window): the loss then computes its targets itself, as without this call."""
-    _require_cuda(imgs=imgs)
+    need_cuda(imgs=imgs)
     if _TLS.wait_free or not fused_supported(pairwise_size, pairwise_dilation):
         return None
     dev = imgs.device
@@ -517,7 +498,7 @@ class BoxInstMaskLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mask_logits: torch.Tensor, imgs: Optional[torch.Tensor], img_metas, gt_inds: torch.Tensor,
                 gt_bboxes, cfg: Dict, affinity_bits: Optional[torch.Tensor]):
-        _require_cuda(mask_logits=mask_logits, imgs=imgs, gt_inds=gt_inds, affinity_bits=affinity_bits)
+        need_cuda(mask_logits=mask_logits, imgs=imgs, gt_inds=gt_inds, affinity_bits=affinity_bits)
         ctx.in_dtype = mask_logits.dtype
         ctx.cfg = cfg
         ctx.fused = affinity_bits is None
@@ -534,7 +515,7 @@ class BoxInstMaskLoss(torch.autograd.Function):
     def _evaluate(ctx, need_grad: bool):
         cfg, logits = ctx.cfg, ctx.logits
         dev = logits.device
-        stream = _current_stream(dev)
+        stream = current_stream(dev)
         imgs, x = _f32c(ctx.imgs), _f32c(logits)
         gi = ctx.gt_inds
         if gi.dtype != torch.int64 or gi.device != dev or not gi.is_contiguous():
@@ -620,7 +601,7 @@ class BoxInstMaskLoss(torch.autograd.Function):
             _lib.check('bxi_boxinst_loss_fwd_bwd_f32', lib.bxi_boxinst_loss_fwd_bwd_f32(
                 C.byref(inst.struct), bits.data_ptr(), size, dil, float(cfg['warmup_factor']),
                 losses.data_ptr(), 0 if grad is None else grad.data_ptr(),
-                0 if state is None else state.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+                0 if state is None else state.data_ptr(), ws.data_ptr(), ws.numel(), current_stream(dev)))
         ctx.inst, ctx.dil, ctx.grad, ctx.state_t = inst, dil, grad, state
         return losses[0], losses[1]
 
@@ -651,7 +632,7 @@ class BoxInstMaskLoss(torch.autograd.Function):
             x = keep[1]
             # (N, h, w) is all the rescale needs of the instances: nothing of the shape class's shared plan is touched here
             args = (x.size(0), x.size(2), x.size(3), g_prj.data_ptr(), g_pw.data_ptr(), int(ctx.cfg['pairwise_dilation']), state,
-                    grad.data_ptr(), _current_stream(dev))
+                    grad.data_ptr(), current_stream(dev))
             if torch.cuda.current_device() == dev.index:          # the usual case: no device guard to set up and tear down
                 rc = plan.rescale_nhw(*args)
             else:
@@ -677,7 +658,7 @@ class BoxInstMaskLoss(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _lib.check('bxi_boxinst_loss_backward_f32', _lib.load().bxi_boxinst_loss_backward_f32(
                     C.byref(inst.struct), g_prj.data_ptr(), g_pw.data_ptr(), ctx.dil, ctx.state_t.data_ptr(),
-                    grad.data_ptr(), _stream(dev)))
+                    grad.data_ptr(), current_stream(dev)))
         if grad.dtype != ctx.in_dtype:
             grad = grad.to(ctx.in_dtype)
         return grad, None, None, None, None, None, None
@@ -693,7 +674,7 @@ class HeadBoxInstLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, params, coors, level_inds, img_inds, sizes_of_interest, head_cfg, imgs, img_metas, gt_inds,
                 gt_bboxes, cfg):
-        _require_cuda(feat=feat, params=params, coors=coors, imgs=imgs, gt_inds=gt_inds)
+        need_cuda(feat=feat, params=params, coors=coors, imgs=imgs, gt_inds=gt_inds)
         dev = feat.device
         in_stride, factor, no_rel = head_cfg
         B, Cf, Hs, Ws = feat.shape
@@ -704,7 +685,7 @@ class HeadBoxInstLoss(torch.autograd.Function):
         lvl, img, soi, gi = i64(level_inds), i64(img_inds), f32(sizes_of_interest), i64(gt_inds)
         boxes = [b.detach().to(device=dev, dtype=torch.float32).contiguous() for b in gt_bboxes]
         imgs_c = _f32c(imgs)
-        stream = _current_stream(dev)
+        stream = current_stream(dev)
         logits = torch.empty((N, 1, Hs * factor, Ws * factor), dtype=torch.float32, device=dev)
         plan = _eval_plan(imgs_c, img_metas, logits, boxes, int(cfg['out_stride']), int(cfg['bottom_pixels_removed']), stream)
         need_grad = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
@@ -739,7 +720,7 @@ class HeadBoxInstLoss(torch.autograd.Function):
         feat, params, coors, lvl, img, soi = ctx.saved_tensors
         dev = feat.device
         lib = _lib.load()
-        stream = _current_stream(dev)
+        stream = current_stream(dev)
         grad, plan, state = ctx.grad, ctx.plan, ctx.state
         ctx.grad = None
         if ctx.calls > 0:

@@ -10,17 +10,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._common import current_stream, need_cuda
 from .registry import LOSSES
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
 
 
 def _f32(t):
@@ -30,7 +21,7 @@ def _f32(t):
 class _Projection(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scores, bitmask, weight):
-        _need_cuda(mask_scores=scores, box_bitmask=bitmask)
+        need_cuda(mask_scores=scores, box_bitmask=bitmask)
         dev = scores.device
         s, b = _f32(scores), _f32(bitmask)
         if s.dim() != 4 or s.size(1) != 1 or b.shape != s.shape:
@@ -41,7 +32,7 @@ class _Projection(torch.autograd.Function):
         state = torch.empty(max(lib.bxi_mil_loss_state_bytes(N, H, W), 16), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
             _lib.check('bxi_projection_loss_forward_f32', lib.bxi_projection_loss_forward_f32(
-                s.data_ptr(), b.data_ptr(), N, H, W, float(weight), loss.data_ptr(), state.data_ptr(), _stream(dev)))
+                s.data_ptr(), b.data_ptr(), N, H, W, float(weight), loss.data_ptr(), state.data_ptr(), current_stream(dev)))
         ctx.save_for_backward(state)
         ctx.meta = (N, H, W, scores.dtype)
         return loss
@@ -55,7 +46,7 @@ class _Projection(torch.autograd.Function):
         gi = torch.empty((N, 1, H, W), dtype=torch.float32, device=state.device)
         with torch.cuda.device(state.device):
             _lib.check('bxi_mil_loss_backward_f32', _lib.load().bxi_mil_loss_backward_f32(
-                N, H, W, state.data_ptr(), g.data_ptr(), gi.data_ptr(), _stream(state.device)))
+                N, H, W, state.data_ptr(), g.data_ptr(), gi.data_ptr(), current_stream(state.device)))
         return gi.to(dtype), None, None
 
 
@@ -73,7 +64,7 @@ class BoxProjectionLoss(torch.nn.Module):
 class _Levelset(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mask_score, target, pixel_num, weight):
-        _need_cuda(mask_logits=mask_score, targets=target, pixel_num=pixel_num)
+        need_cuda(mask_logits=mask_score, targets=target, pixel_num=pixel_num)
         dev = mask_score.device
         m, t, pn = _f32(mask_score), _f32(target), _f32(pixel_num).view(-1)
         if m.dim() != 4 or m.size(1) != 2 or t.dim() != 4 or t.shape[0] != m.shape[0] or t.shape[2:] != m.shape[2:]:
@@ -87,7 +78,7 @@ class _Levelset(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check('bxi_levelset_loss_forward_f32', lib.bxi_levelset_loss_forward_f32(
                 m.data_ptr(), t.data_ptr(), pn.data_ptr(), N, C, H, W, float(weight), loss.data_ptr(), state.data_ptr(),
-                _stream(dev)))
+                current_stream(dev)))
         ctx.save_for_backward(m, t, pn, state)
         ctx.meta = (float(weight), mask_score.dtype, target.dtype)
         return loss
@@ -104,7 +95,7 @@ class _Levelset(torch.autograd.Function):
         with torch.cuda.device(m.device):
             _lib.check('bxi_levelset_loss_backward_f32', _lib.load().bxi_levelset_loss_backward_f32(
                 m.data_ptr(), t.data_ptr(), pn.data_ptr(), N, C, H, W, weight, state.data_ptr(), g.data_ptr(), gm.data_ptr(),
-                0 if gt is None else gt.data_ptr(), _stream(m.device)))
+                0 if gt is None else gt.data_ptr(), current_stream(m.device)))
         return gm.to(dm), (None if gt is None else gt.to(dt)), None, None
 
 
@@ -134,7 +125,7 @@ def _refine(aff, phi, dilation, iters, transpose):
     with torch.cuda.device(phi.device):
         _lib.check('bxi_lcm_refine_f32', lib.bxi_lcm_refine_f32(
             aff.data_ptr(), phi.data_ptr(), N, h, w, int(dilation), int(iters), int(transpose), out.data_ptr(), ws.data_ptr(),
-            ws.numel(), _stream(phi.device)))
+            ws.numel(), current_stream(phi.device)))
     return out
 
 
@@ -168,17 +159,17 @@ class LocalConsistencyModule(torch.nn.Module):
         self.alpha = 0.3
 
     def affinity(self, imgs):
-        _need_cuda(imgs=imgs)
+        need_cuda(imgs=imgs)
         x = _f32(imgs)
         N, C, h, w = x.shape
         aff = torch.empty((N, 8, h, w), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check('bxi_lcm_affinity_f32', _lib.load().bxi_lcm_affinity_f32(
-                x.data_ptr(), N, C, h, w, int(self.dilations[0]), float(self.alpha), aff.data_ptr(), _stream(x.device)))
+                x.data_ptr(), N, C, h, w, int(self.dilations[0]), float(self.alpha), aff.data_ptr(), current_stream(x.device)))
         return aff
 
     def forward(self, imgs, pred_phis):
-        _need_cuda(pred_phis=pred_phis)
+        need_cuda(pred_phis=pred_phis)
         if pred_phis.dim() != 4 or pred_phis.size(1) != 1:
             raise RuntimeError('pred_phis must be [N,1,h,w]')
         return _LcmRefine.apply(self.affinity(imgs), pred_phis, self.dilations[0], self.num_iter)

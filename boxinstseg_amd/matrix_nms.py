@@ -17,19 +17,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._common import cfg_require, current_stream, need_cuda
 
 __all__ = ['mask_matrix_nms', 'seg_nms', 'pack_probs', 'pack_masks', 'matrix_nms_decay', 'matrix_nms_scores',
            'box_solov2_get_seg_single', 'discobox_get_seg_single']
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
 
 
 def _words(h: int, w: int) -> int:
@@ -39,7 +30,7 @@ def _words(h: int, w: int) -> int:
 def pack_probs(seg_preds: torch.Tensor, mask_thr: float):
     """``seg_preds`` [n,h,w] fp32 -> (bits [n, ceil(hw/64)] int64, area [n] int32, psum [n] fp32): ``seg_preds > mask_thr`` as bits,
     its pixel count, and the sum of the probabilities over the set pixels -- one pass, no boolean or fp32 mask tensor."""
-    _need_cuda(seg_preds=seg_preds)
+    need_cuda(seg_preds=seg_preds)
     if seg_preds.dim() != 3 or seg_preds.dtype != torch.float32:
         raise RuntimeError(f'seg_preds must be fp32 [n,h,w], got {seg_preds.dtype} {tuple(seg_preds.shape)}')
     dev = seg_preds.device
@@ -50,13 +41,13 @@ def pack_probs(seg_preds: torch.Tensor, mask_thr: float):
     psum = torch.empty(n, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check('bxi_mask_pack_f32', _lib.load().bxi_mask_pack_f32(p.data_ptr(), n, h, w, float(mask_thr), bits.data_ptr(),
-                                                                      area.data_ptr(), psum.data_ptr(), _stream(dev)))
+                                                                      area.data_ptr(), psum.data_ptr(), current_stream(dev)))
     return bits, area, psum
 
 
 def pack_masks(masks: torch.Tensor):
     """``masks`` [n,h,w] bool / uint8 (non-zero = set) -> (bits, area)."""
-    _need_cuda(masks=masks)
+    need_cuda(masks=masks)
     if masks.dim() != 3 or masks.dtype not in (torch.bool, torch.uint8):
         raise RuntimeError(f'masks must be bool or uint8 [n,h,w], got {masks.dtype} {tuple(masks.shape)}')
     dev = masks.device
@@ -66,7 +57,7 @@ def pack_masks(masks: torch.Tensor):
     bits = torch.empty((n, _words(h, w)), dtype=torch.int64, device=dev)
     area = torch.empty(n, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        _lib.check('bxi_mask_pack_u8', _lib.load().bxi_mask_pack_u8(m.data_ptr(), n, h, w, bits.data_ptr(), area.data_ptr(), _stream(dev)))
+        _lib.check('bxi_mask_pack_u8', _lib.load().bxi_mask_pack_u8(m.data_ptr(), n, h, w, bits.data_ptr(), area.data_ptr(), current_stream(dev)))
     return bits, area
 
 
@@ -80,7 +71,7 @@ def matrix_nms_decay(bits, area, labels, order, scores_sorted, hw, kernel='gauss
     """The kernels of matrix_nms.py:60-99 on packed masks: ``order`` [n] indexes the candidates of ``bits`` / ``area`` / ``labels``
     by descending score, ``scores_sorted`` [n] are their scores, ``hw`` = (h, w).  Returns (decayed [n], decay_iou [n,n],
     compensate [n]); ``compensate`` is a view of the call's workspace."""
-    _need_cuda(bits=bits, area=area, labels=labels, order=order, scores_sorted=scores_sorted)
+    need_cuda(bits=bits, area=area, labels=labels, order=order, scores_sorted=scores_sorted)
     kid = _kernel_id(kernel)
     dev = bits.device
     n_all, n = bits.size(0), order.numel()
@@ -101,7 +92,7 @@ def matrix_nms_decay(bits, area, labels, order, scores_sorted, hw, kernel='gauss
     with torch.cuda.device(dev):
         _lib.check('bxi_matrix_nms_f32', lib.bxi_matrix_nms_f32(
             bits.data_ptr(), area.data_ptr(), labels.data_ptr(), order.data_ptr(), scores_sorted.data_ptr(), n_all, n, h, w, kid,
-            float(sigma), decayed.data_ptr(), decay_iou.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream(dev)))
+            float(sigma), decayed.data_ptr(), decay_iou.data_ptr(), ws.data_ptr(), ws.numel() * 4, current_stream(dev)))
     return decayed, decay_iou, ws[:n]
 
 
@@ -140,7 +131,7 @@ def mask_matrix_nms(masks, labels, scores, filter_thr=-1, nms_pre=-1, max_num=-1
     index goes first, which is one of the orders the reference's unstable sort may produce.  At most 2048 candidates enter the
     n x n stage (after ``nms_pre``)."""
     _kernel_id(kernel)
-    _need_cuda(masks=masks, labels=labels, scores=scores, mask_area=mask_area)
+    need_cuda(masks=masks, labels=labels, scores=scores, mask_area=mask_area)
     assert len(labels) == len(masks) == len(scores)
     if len(labels) == 0:
         return scores.new_zeros(0), labels.new_zeros(0), masks.new_zeros(0, *masks.shape[-2:]), labels.new_zeros(0)
@@ -156,37 +147,33 @@ def mask_matrix_nms(masks, labels, scores, filter_thr=-1, nms_pre=-1, max_num=-1
     return out_scores.to(scores.dtype), labels[keep_inds], masks[keep_inds], keep_inds
 
 
-def _get(cfg, name):
-    return cfg[name] if isinstance(cfg, dict) else getattr(cfg, name)
-
-
 def seg_nms(seg_preds, cate_labels, cate_scores, strides, cfg):
     """The block ``seg_masks = seg_preds > cfg.mask_thr`` ... ``mask_matrix_nms(...)`` of the SOLOv2-style heads
     (box_solov2_head.py:546-574), fused: threshold, bits, area and the mask-score numerator in one pass over ``seg_preds`` [n,h,w];
     ``sum_masks > strides``; ``cate_scores * psum / area``; Matrix NMS through the surviving rows.  Returns
     ``(scores, labels, keep_inds)`` with ``keep_inds`` indexing the n input candidates; empty tensors when nothing survives.
     ``cfg`` holds mask_thr, filter_thr, nms_pre, max_per_img, kernel, sigma (attributes or keys)."""
-    kernel, sigma = _get(cfg, 'kernel'), _get(cfg, 'sigma')
+    kernel, sigma = cfg_require(cfg, 'kernel'), cfg_require(cfg, 'sigma')
     _kernel_id(kernel)
-    _need_cuda(seg_preds=seg_preds, cate_labels=cate_labels, cate_scores=cate_scores, strides=strides)
+    need_cuda(seg_preds=seg_preds, cate_labels=cate_labels, cate_scores=cate_scores, strides=strides)
     n = seg_preds.size(0)
     assert len(cate_labels) == len(cate_scores) == len(strides) == n
     empty = (cate_scores.new_zeros(0), cate_labels.new_zeros(0), cate_labels.new_zeros(0))
     if n == 0:
         return empty
-    bits, area, psum = pack_probs(seg_preds, _get(cfg, 'mask_thr'))
+    bits, area, psum = pack_probs(seg_preds, cfg_require(cfg, 'mask_thr'))
     sum_masks = area.float()
     kept = (sum_masks > strides).nonzero(as_tuple=True)[0]
     if kept.numel() == 0:
         return empty
     scores = cate_scores[kept].float() * (psum[kept] / sum_masks[kept])
     sorted_scores, sort_inds = torch.sort(scores, descending=True, stable=True)
-    nms_pre = _get(cfg, 'nms_pre')
+    nms_pre = cfg_require(cfg, 'nms_pre')
     if nms_pre > 0 and sort_inds.numel() > nms_pre:
         sort_inds, sorted_scores = sort_inds[:nms_pre], sorted_scores[:nms_pre]
     order = kept[sort_inds]
     decayed, _, _ = matrix_nms_decay(bits, area, cate_labels, order, sorted_scores, seg_preds.shape[-2:], kernel, sigma)
-    done = _finish(decayed, order, _get(cfg, 'filter_thr'), _get(cfg, 'max_per_img'))
+    done = _finish(decayed, order, cfg_require(cfg, 'filter_thr'), cfg_require(cfg, 'max_per_img'))
     if done is None:
         return empty
     out_scores, keep_inds = done
@@ -223,7 +210,7 @@ def _seg_tail(seg_preds, cate_labels, cate_scores, strides, featmap_size, img_me
         return _empty_results(img_meta, cate_scores)
     up = (featmap_size[0] * 4, featmap_size[1] * 4)
     kept = F.interpolate(seg_preds[keep_inds].unsqueeze(0), size=up, mode='bilinear')[:, :, :h, :w]
-    masks = F.interpolate(kept, size=tuple(ori_shape[:2]), mode='bilinear').squeeze(0) > _get(cfg, 'mask_thr')
+    masks = F.interpolate(kept, size=tuple(ori_shape[:2]), mode='bilinear').squeeze(0) > cfg_require(cfg, 'mask_thr')
     return _results(img_meta, scores, labels, masks)
 
 
@@ -231,9 +218,9 @@ def box_solov2_get_seg_single(cate_preds, seg_preds, featmap_size, img_meta, cfg
     """``BoxSOLOv2Head.get_seg_single`` (box_solov2_head.py:503-590).  ``cate_preds`` [sum(grid^2), classes], ``seg_preds``
     [sum(grid^2), h, w] probabilities, ``seg_num_grids`` / ``strides`` the head's per-level settings.  Returns an object with
     ``scores``, ``labels``, ``masks`` (bool [n, ori_h, ori_w]) and the image's ``img_shape`` / ``ori_shape``."""
-    _need_cuda(cate_preds=cate_preds, seg_preds=seg_preds)
+    need_cuda(cate_preds=cate_preds, seg_preds=seg_preds)
     assert len(cate_preds) == len(seg_preds)
-    inds = cate_preds > _get(cfg, 'score_thr')
+    inds = cate_preds > cfg_require(cfg, 'score_thr')
     cate_scores = cate_preds[inds]
     if len(cate_scores) == 0:
         return _empty_results(img_meta, cate_scores)
@@ -247,9 +234,9 @@ def discobox_get_seg_single(cate_preds, seg_preds, kernel_preds, featmap_size, i
     """``DiscoBoxSOLOv2Head.get_seg_single`` (discobox_head.py:1560-1660).  ``seg_preds`` [1, C, h, w] is the mask feature and
     ``kernel_preds`` [sum(grid^2), C] the dynamic 1x1 kernels; the convolution and the sigmoid run in torch in the tensors' own
     precision (the reference runs this method under autocast), the block after them through ``seg_nms`` in fp32."""
-    _need_cuda(cate_preds=cate_preds, seg_preds=seg_preds, kernel_preds=kernel_preds)
+    need_cuda(cate_preds=cate_preds, seg_preds=seg_preds, kernel_preds=kernel_preds)
     assert len(cate_preds) == len(kernel_preds)
-    inds = cate_preds > _get(cfg, 'score_thr')
+    inds = cate_preds > cfg_require(cfg, 'score_thr')
     cate_scores = cate_preds[inds]
     if len(cate_scores) == 0:
         return _empty_results(img_meta, cate_scores)

@@ -20,6 +20,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._common import current_stream
 
 _SUFFIX = {torch.float32: 'f32', torch.float64: 'f64'}
 
@@ -44,8 +45,7 @@ def _geometry(logits: torch.Tensor, size: int):
 def _call(name: str, logits: torch.Tensor, *args) -> None:
     fn = f'{name}_{_SUFFIX[logits.dtype]}'
     with torch.cuda.device(logits.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(fn, getattr(_lib.load(), fn)(*args, stream))
+        _lib.check(fn, getattr(_lib.load(), fn)(*args, current_stream(logits.device)))
 
 
 def pairwise_nlog_forward(pairwise_size: int, pairwise_dilation: int, logits: torch.Tensor) -> torch.Tensor:

@@ -24,7 +24,7 @@ import math
 import torch
 
 from . import _lib
-from .box_head_loss import _get, _need_cuda, _only, _stream
+from ._common import cfg_get, cfg_only, current_stream, need_cuda
 
 __all__ = ['solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets', 'RESCALE_MIN_ONES']
 
@@ -37,35 +37,35 @@ def parse_solo_head_cfg(cfg):
     """``bbox_head=dict(type='DiscoBoxSOLOv2Head' | 'BoxSOLOv2Head', ...)`` (dict or namespace) -> the flat settings the functions here
     take: mode, num_classes, strides, scale_ranges, num_grids, sigma, gamma, alpha, loss_weight_cate.  Keys that shape the network or
     belong to the other losses are accepted and ignored.  A ``loss_cate`` that is not the sigmoid focal loss raises NotImplementedError."""
-    kind = _get(cfg, 'type')
+    kind = cfg_get(cfg, 'type')
     if kind not in _HEADS:
         raise NotImplementedError(f'bbox_head.type {kind!r} is not supported: one of {sorted(_HEADS)}')
-    num_classes = _get(cfg, 'num_classes')
+    num_classes = cfg_get(cfg, 'num_classes')
     if num_classes is None:
         raise TypeError('bbox_head has no `num_classes`')
-    num_grids = _get(cfg, 'num_grids')
+    num_grids = cfg_get(cfg, 'num_grids')
     if num_grids is None:
         raise TypeError('bbox_head has no `num_grids`')
-    strides = [int(s) for s in _get(cfg, 'strides', (4, 8, 16, 32, 64))]
-    ranges = tuple((float(a), float(b)) for a, b in _get(cfg, 'scale_ranges', ((8, 32), (16, 64), (32, 128), (64, 256), (128, 512))))
+    strides = [int(s) for s in cfg_get(cfg, 'strides', (4, 8, 16, 32, 64))]
+    ranges = tuple((float(a), float(b)) for a, b in cfg_get(cfg, 'scale_ranges', ((8, 32), (16, 64), (32, 128), (64, 256), (128, 512))))
     num_grids = [int(s) for s in num_grids]
     if not len(strides) == len(ranges) == len(num_grids):
         raise TypeError(f'{len(strides)} strides, {len(ranges)} scale_ranges and {len(num_grids)} num_grids')
-    lc = _get(cfg, 'loss_cate')
+    lc = cfg_get(cfg, 'loss_cate')
     if lc is None:
         raise TypeError('bbox_head has no `loss_cate`')
-    if _get(lc, 'type') != 'FocalLoss':
-        raise NotImplementedError(f"loss_cate.type {_get(lc, 'type')!r} is not supported: only 'FocalLoss'")
-    _only(lc, 'loss_cate', ('type', 'use_sigmoid', 'gamma', 'alpha', 'loss_weight', 'reduction', 'activated'))
-    if not _get(lc, 'use_sigmoid', True):
+    if cfg_get(lc, 'type') != 'FocalLoss':
+        raise NotImplementedError(f"loss_cate.type {cfg_get(lc, 'type')!r} is not supported: only 'FocalLoss'")
+    cfg_only(lc, 'loss_cate', ('type', 'use_sigmoid', 'gamma', 'alpha', 'loss_weight', 'reduction', 'activated'))
+    if not cfg_get(lc, 'use_sigmoid', True):
         raise NotImplementedError('loss_cate.use_sigmoid=False is not supported')
-    if _get(lc, 'activated', False):
+    if cfg_get(lc, 'activated', False):
         raise NotImplementedError('loss_cate.activated=True is not supported')
-    if _get(lc, 'reduction', 'mean') != 'mean':
+    if cfg_get(lc, 'reduction', 'mean') != 'mean':
         raise NotImplementedError("loss_cate.reduction: only 'mean' is supported")
     return dict(mode=_HEADS[kind], num_classes=int(num_classes), strides=strides, scale_ranges=ranges, num_grids=num_grids,
-                sigma=float(_get(cfg, 'sigma', 0.2)), gamma=float(_get(lc, 'gamma', 2.0)), alpha=float(_get(lc, 'alpha', 0.25)),
-                loss_weight_cate=float(_get(lc, 'loss_weight', 1.0)))
+                sigma=float(cfg_get(cfg, 'sigma', 0.2)), gamma=float(cfg_get(lc, 'gamma', 2.0)), alpha=float(cfg_get(lc, 'alpha', 0.25)),
+                loss_weight_cate=float(cfg_get(lc, 'loss_weight', 1.0)))
 
 
 class SoloTargets:
@@ -131,7 +131,7 @@ def _targets(mode, gt_bboxes, gt_labels, gt_masks, level_sizes, canvas, *, scale
     for i, (bx, lb) in enumerate(zip(gt_bboxes, gt_labels)):
         if not isinstance(bx, torch.Tensor) or not isinstance(lb, torch.Tensor):
             raise TypeError(f'gt_bboxes[{i}] / gt_labels[{i}] is not a tensor')
-    _need_cuda(**{f'gt_bboxes[{i}]': t for i, t in enumerate(gt_bboxes)}, **{f'gt_labels[{i}]': t for i, t in enumerate(gt_labels)})
+    need_cuda(**{f'gt_bboxes[{i}]': t for i, t in enumerate(gt_bboxes)}, **{f'gt_labels[{i}]': t for i, t in enumerate(gt_labels)})
     dev = gt_bboxes[0].device
     masks = [_as_mask_tensor(m, dev, i) for i, m in enumerate(gt_masks)]
     # the factor of every level and the plane size of every factor
@@ -184,7 +184,7 @@ def _targets(mode, gt_bboxes, gt_labels, gt_masks, level_sizes, canvas, *, scale
     lib = _lib.load()
     ptr = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()                  # noqa: E731
     with torch.cuda.device(dev):
-        st = _stream(dev)
+        st = current_stream(dev)
         _lib.check('bxi_solo_mask_pass_u8', lib.bxi_solo_mask_pass_u8(
             _lib.ptr_array([ptr(m) or 0 for m in masks]), _lib.int_array(offsets), _lib.int_array([m.shape[1] for m in masks]),
             _lib.int_array([m.shape[2] for m in masks]), B, _lib.int_array(factors), _lib.int_array([planes[f][0] for f in factors]),
@@ -280,7 +280,7 @@ class _CateLoss(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check('bxi_solo_cate_loss_f32', lib.bxi_solo_cate_loss_f32(
                 _lib.ptr_array([m.data_ptr() for m in maps]), grids, n, B, C, labels.data_ptr(), num_ins.data_ptr(), gamma, alpha, loss_weight,
-                _lib.ptr_array([u.data_ptr() for u in unit]), loss.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)))
+                _lib.ptr_array([u.data_ptr() for u in unit]), loss.data_ptr(), ws.data_ptr(), nbytes, current_stream(dev)))
         ctx.unit, ctx.grids, ctx.shape = unit, grids, (n, B, C)
         return loss[0]
 
@@ -294,7 +294,7 @@ class _CateLoss(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check('bxi_solo_cate_grad_rescale_f32', _lib.load().bxi_solo_cate_grad_rescale_f32(
                 ctx.grids, n, B, C, _lib.ptr_array([u.data_ptr() for u in unit]), up.data_ptr(), _lib.ptr_array([o.data_ptr() for o in out]),
-                _stream(dev)))
+                current_stream(dev)))
         return (None, None, None, None, None, *out)
 
 
@@ -312,7 +312,7 @@ def solo_cate_loss(cate_preds, cate_labels, num_ins, gamma=2.0, alpha=0.25, loss
         cate_labels = torch.cat([t.reshape(-1) for t in cate_labels])
     if not isinstance(cate_labels, torch.Tensor) or not isinstance(num_ins, torch.Tensor):
         raise TypeError('cate_labels and num_ins must be tensors')
-    _need_cuda(**{f'cate_preds[{i}]': t for i, t in enumerate(cate_preds)}, cate_labels=cate_labels, num_ins=num_ins)
+    need_cuda(**{f'cate_preds[{i}]': t for i, t in enumerate(cate_preds)}, cate_labels=cate_labels, num_ins=num_ins)
     for name, v in (('gamma', gamma), ('alpha', alpha), ('loss_weight', loss_weight)):
         if math.isnan(float(v)):
             raise RuntimeError(f'{name} is NaN')

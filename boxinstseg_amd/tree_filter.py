@@ -11,22 +11,13 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _need_cuda(**tensors):
-    for name, t in tensors.items():
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'{name} must be a CUDA (HIP) tensor: boxinstseg_amd has no CPU path')
+from ._common import current_stream, need_cuda
 
 
 def mst(edge_index, edge_weight, vertex_count):
     """``mst(edge_index [B,E,2] int32, edge_weight [B,E], vertex_count)`` -> tree edges [B,V-1,2] int32 (functions/mst.py).
     Computed on the GPU (the reference round-trips through the host); the edges are listed in ascending edge order."""
-    _need_cuda(edge_index=edge_index, edge_weight=edge_weight)
+    need_cuda(edge_index=edge_index, edge_weight=edge_weight)
     dev = edge_index.device
     idx = edge_index.detach().to(torch.int32).contiguous()
     w = edge_weight.detach().to(torch.float32).contiguous()
@@ -37,12 +28,12 @@ def mst(edge_index, edge_weight, vertex_count):
     ws = torch.empty(max(lib.bxi_mst_workspace_bytes(B, E, V), 16), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         _lib.check('bxi_mst_forward_i32', lib.bxi_mst_forward_i32(idx.data_ptr(), w.data_ptr(), B, E, V, out.data_ptr(), ws.data_ptr(),
-                                                                   ws.numel(), _stream(dev)))
+                                                                   ws.numel(), current_stream(dev)))
     return out
 
 
 def _bfs_levels(edge_index, max_adj_per_vertex):
-    _need_cuda(edge_index=edge_index)
+    need_cuda(edge_index=edge_index)
     dev = edge_index.device
     tree = edge_index.detach().to(torch.int32).contiguous()
     B, V = tree.size(0), tree.size(1) + 1
@@ -55,7 +46,7 @@ def _bfs_levels(edge_index, max_adj_per_vertex):
     with torch.cuda.device(dev):
         _lib.check('bxi_bfs_forward_i32', lib.bxi_bfs_forward_i32(tree.data_ptr(), B, V, int(max_adj_per_vertex), si.data_ptr(),
                                                                    sp.data_ptr(), sc.data_ptr(), lv.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                                   _stream(dev)))
+                                                                   current_stream(dev)))
     return si, sp, sc, lv
 
 
@@ -95,7 +86,7 @@ def _levels_of(sorted_index, sorted_parent):
 class _Refine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feature_in, edge_weight, sorted_index, sorted_parent, sorted_child, low_tree, levels):
-        _need_cuda(feature_in=feature_in, edge_weight=edge_weight, sorted_index=sorted_index)
+        need_cuda(feature_in=feature_in, edge_weight=edge_weight, sorted_index=sorted_index)
         dev = feature_in.device
         x = feature_in.detach().to(torch.float32).contiguous()
         w = edge_weight.detach().to(torch.float32).contiguous()
@@ -110,7 +101,7 @@ class _Refine(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check('bxi_tree_refine_forward_f32', lib.bxi_tree_refine_forward_f32(
                 x.data_ptr(), w.data_ptr(), si.data_ptr(), sc.data_ptr(), levels.data_ptr(), B, C, V, A, out.data_ptr(), aggr.data_ptr(),
-                aggr_up.data_ptr(), wsum.data_ptr(), wsum_up.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+                aggr_up.data_ptr(), wsum.data_ptr(), wsum_up.data_ptr(), ws.data_ptr(), ws.numel(), current_stream(dev)))
         ctx.save_for_backward(w, si, sp, sc, levels, out, aggr, aggr_up, wsum, wsum_up)
         ctx.low_tree = low_tree
         ctx.dtypes = (feature_in.dtype, edge_weight.dtype)
@@ -132,7 +123,7 @@ class _Refine(torch.autograd.Function):
             with torch.cuda.device(dev):
                 _lib.check('bxi_tree_refine_backward_feature_f32', lib.bxi_tree_refine_backward_feature_f32(
                     g.data_ptr(), w.data_ptr(), si.data_ptr(), sc.data_ptr(), levels.data_ptr(), wsum.data_ptr(), B, C, V, A, gf.data_ptr(),
-                    ws.data_ptr(), ws.numel(), _stream(dev)))
+                    ws.data_ptr(), ws.numel(), current_stream(dev)))
         else:                           # both gradients from one launch (the weight gradient's first traversal is the feature gradient)
             gw = torch.empty_like(w)
             ws = torch.empty(max(lib.bxi_tree_refine_backward_weight_workspace_bytes(B, C, V), 16), dtype=torch.uint8, device=dev)
@@ -140,7 +131,7 @@ class _Refine(torch.autograd.Function):
                 _lib.check('bxi_tree_refine_backward_weight_f32', lib.bxi_tree_refine_backward_weight_f32(
                     g.data_ptr(), w.data_ptr(), si.data_ptr(), sp.data_ptr(), sc.data_ptr(), levels.data_ptr(), out.data_ptr(),
                     aggr.data_ptr(), aggr_up.data_ptr(), wsum.data_ptr(), wsum_up.data_ptr(), B, C, V, A, gw.data_ptr(), gf.data_ptr(),
-                    ws.data_ptr(), ws.numel(), _stream(dev)))
+                    ws.data_ptr(), ws.numel(), current_stream(dev)))
             gw = gw.to(ctx.dtypes[1])
         return gf.to(ctx.dtypes[0]), gw, None, None, None, None, None
 

@@ -22,7 +22,7 @@ from tests.helpers import expected_grad_logit_first, grad_check_all_lines, grad_
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
-# entry point -> the test of this module that runs it guarded (tests/test_guarded_complete.py walks _lib.SIGNATURES)
+# entry point -> the test of this module that runs it guarded (tests/test_abi_families.py checks the table against _lib.SIGNATURES)
 GUARDED = {
     'bxi_pairwise_nlog_forward_f32': 'test_pairwise_forward_guarded',
     'bxi_pairwise_nlog_forward_f64': 'test_pairwise_forward_guarded',

@@ -14,7 +14,7 @@ from tests import guarded as G
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_box_head_loss.py checks the table against _lib.FCOS_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.FCOS_SIGNATURES)
 GUARDED = {
     'bxi_fcos_targets_f32': 'test_targets_guarded',
     'bxi_fcos_loss_f32': 'test_loss_guarded',

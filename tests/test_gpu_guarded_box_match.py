@@ -12,7 +12,7 @@ from tests import guarded as G
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_box_match.py checks the table against _lib.ASSIGN_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.ASSIGN_SIGNATURES)
 GUARDED = {
     'bxi_match_project_pred_f32': 'test_project_pred_guarded',
     'bxi_match_project_gt_u8': 'test_project_gt_u8_guarded',

@@ -13,7 +13,7 @@ from tests import guarded as G
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_det.py checks the table against _lib.DET_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.DET_SIGNATURES)
 GUARDED = {
     'bxi_det_location_score_f32': 'test_location_score_guarded',
     'bxi_det_candidates_f32': 'test_candidates_guarded',

@@ -22,7 +22,7 @@ from tests import guarded as G
 pytestmark = pytest.mark.gpu
 SOI = [64, 128, 256, 512, 1024]
 
-# entry point -> the test of this module that runs it guarded (tests/test_guarded_complete.py walks _lib.SIGNATURES)
+# entry point -> the test of this module that runs it guarded (tests/test_abi_families.py checks the table against _lib.SIGNATURES)
 GUARDED = {
     'bxi_dynamic_mask_forward_f32': 'test_dynamic_head_guarded',
     'bxi_dynamic_mask_backward_f32': 'test_dynamic_head_guarded',

@@ -13,7 +13,7 @@ from tests import matrix_nms_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_matrix_nms.py checks the table against _lib.POST_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.POST_SIGNATURES)
 GUARDED = {
     'bxi_mask_pack_f32': 'test_mask_pack_f32_guarded',
     'bxi_mask_pack_u8': 'test_mask_pack_u8_guarded',

@@ -13,7 +13,7 @@ from tests import solo_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_solo_targets.py checks the table against _lib.SOLO_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.SOLO_SIGNATURES)
 GUARDED = {
     'bxi_solo_mask_pass_u8': 'test_mask_pass_guarded',
     'bxi_solo_assign_f32': 'test_assign_guarded',

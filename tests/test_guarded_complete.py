@@ -1,67 +1,9 @@
-"""Host side of the guarded tests: every entry point of the C ABI is either run guarded by a named test or exempt for a stated reason,
-and the helper itself (tests/guarded.py) does what it says.  No GPU needed."""
-import inspect
-
+"""Host side of the guarded tests: the helper itself (tests/guarded.py) does what it says.  Which entry point is run guarded by
+which test, or exempt for which reason, is checked in tests/test_abi_families.py.  No GPU needed."""
 import pytest
 import torch
 
 from tests import guarded as G
-
-# entry point -> why no guarded test runs it: nothing here launches a kernel over caller memory
-EXEMPT = {
-    'bxi_abi_version': 'version query',
-    'bxi_status_string': 'status text',
-    'bxi_last_hip_error': 'status query',
-    'bxi_check_device': 'device query',
-    'bxi_dev_set_launch_hook': 'developer hook (bxi_dev_*)',
-    'bxi_dev_set_tree_level_walk': 'developer switch (bxi_dev_*)',
-    'bxi_dev_sol_eval_f32': 'benchmark-only speed-of-light kernel (bxi_dev_*)',
-    'bxi_dev_sol_pairwise_f32': 'benchmark-only speed-of-light kernel (bxi_dev_*)',
-    'bxi_boxinst_loss_workspace_bytes': 'size query',
-    'bxi_boxinst_loss_state_bytes': 'size query',
-    'bxi_boxinst_loss_state_status_offset': 'offset query',
-    'bxi_boxinst_loss_state_warmup_offset': 'offset query',
-    'bxi_boxinst_eval_workspace_bytes': 'size query',
-    'bxi_boxinst_eval_workspace_lab_offset': 'offset query',
-    'bxi_dynamic_mask_backward_workspace_bytes': 'size query',
-    'bxi_dynamic_mask_generic_backward_workspace_bytes': 'size query',
-    'bxi_meanfield_workspace_bytes': 'size query',
-    'bxi_mil_loss_state_bytes': 'size query',
-    'bxi_levelset_state_bytes': 'size query',
-    'bxi_lcm_workspace_bytes': 'size query',
-    'bxi_mst_workspace_bytes': 'size query',
-    'bxi_bfs_workspace_bytes': 'size query',
-    'bxi_tree_refine_workspace_bytes': 'size query',
-    'bxi_tree_refine_backward_weight_workspace_bytes': 'size query',
-}
-
-
-def _tables():
-    from tests import test_gpu_guarded_abi as abi, test_gpu_guarded_modules as mods
-    return {abi: abi.GUARDED, mods: mods.GUARDED}
-
-
-def test_every_entry_point_is_guarded_or_exempt():
-    """A new entry point fails here until somebody decides which of the two it is."""
-    from boxinstseg_amd import _lib
-    tables = _tables()
-    guarded = {}
-    for mod, table in tables.items():
-        for entry, test in table.items():
-            assert entry not in guarded, f'{entry} is listed twice'
-            fn = getattr(mod, test, None)
-            assert callable(fn), f'{entry}: {mod.__name__} has no test {test}'
-            assert entry in inspect.getsource(mod), entry
-            guarded[entry] = test
-    assert not set(guarded) & set(EXEMPT), sorted(set(guarded) & set(EXEMPT))
-    for entry in _lib.SIGNATURES:
-        assert entry in guarded or entry in EXEMPT, f'{entry}: neither run by a guarded test (GUARDED) nor exempt with a reason (EXEMPT)'
-    stale = (set(guarded) | set(EXEMPT)) - set(_lib.SIGNATURES)
-    assert not stale, f'not in _lib.SIGNATURES any more: {sorted(stale)}'
-    for entry, reason in EXEMPT.items():
-        assert reason and ('_bytes' in entry or '_offset' in entry or entry.startswith('bxi_dev_') or entry in
-                           ('bxi_abi_version', 'bxi_status_string', 'bxi_last_hip_error', 'bxi_check_device')), entry
-
 
 @pytest.mark.parametrize('dtype,lead', [(torch.float32, 0), (torch.float32, 3), (torch.float64, 1), (torch.int32, 1), (torch.int64, 1), (torch.uint8, 15)])
 def test_embed_places_the_view_and_the_poison(dtype, lead):

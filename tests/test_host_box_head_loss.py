@@ -7,7 +7,6 @@
 * the bbox_head block of every configs/boxinst file is accepted, an unsupported loss type raises;
 * CPU tensors and bad arguments fail before any launch."""
 import importlib.util
-import inspect
 import json
 import os
 import re
@@ -126,22 +125,11 @@ def test_fixture_is_what_the_reference_computes_now(name):
 
 
 def test_header_exports_and_signatures_agree():
+    """(declarations, exports and ctypes signatures: tests/test_abi_families.py)"""
     from boxinstseg_amd import _lib, box_head_loss
     lib = _lib.load()
     with open(HEADER) as fh:
         text = fh.read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    names = sorted(set(re.findall(r'\b(bxi_fcos_[a-z0-9_]+)\s*\(', code)))
-    assert names, 'no declarations found'
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in boxinst_hip_fcos.h but not exported'
-    assert sorted(_lib.FCOS_SIGNATURES) == names
-    assert not set(_lib.FCOS_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.POST_SIGNATURES) | set(_lib.ASSIGN_SIGNATURES) | set(_lib.DET_SIGNATURES))
-    for n, (res, args) in _lib.FCOS_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        decl = re.search(r'\b' + n + r'\s*\(([^)]*)\)\s*;', code).group(1)
-        assert len([a for a in decl.split(',') if a.strip() and a.strip() != 'void']) == len(args), n
     for macro, value in (('BXI_FCOS_GT_CHUNK', _lib.FCOS_GT_CHUNK), ('BXI_FCOS_LOC_TILE', _lib.FCOS_LOC_TILE), ('BXI_FCOS_ELEM_TILE', _lib.FCOS_ELEM_TILE),
                          ('BXI_FCOS_STATUS_BAD_LABEL', _lib.FCOS_STATUS_BAD_LABEL), ('BXI_FCOS_BBOX_GIOU', _lib.FCOS_BBOX_KINDS['giou']),
                          ('BXI_FCOS_BBOX_IOU_LOG', _lib.FCOS_BBOX_KINDS['iou_log']), ('BXI_FCOS_BBOX_IOU_LINEAR', _lib.FCOS_BBOX_KINDS['iou_linear']),
@@ -158,20 +146,6 @@ def test_header_exports_and_signatures_agree():
         integration = fh.read()
     for word in ('Level 3e', 'not enough values to unpack', 'lowest box index', 'unpinned', 'DIoULoss', 'bxi_fcos_grad_rescale_f32'):
         assert word in integration, word
-
-
-def test_every_fcos_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    from tests import test_gpu_guarded_box_head_loss as guarded
-    for entry in _lib.FCOS_SIGNATURES:
-        if entry.endswith('_bytes'):
-            assert entry not in guarded.GUARDED
-            continue
-        test = guarded.GUARDED.get(entry)
-        assert test, f'{entry}: not run by a guarded test'
-        assert callable(getattr(guarded, test, None)), f'{entry}: test_gpu_guarded_box_head_loss has no test {test}'
-        assert entry in inspect.getsource(getattr(guarded, test)), entry
-    assert not set(guarded.GUARDED) - set(_lib.FCOS_SIGNATURES)
 
 
 def test_reference_head_blocks_are_accepted():

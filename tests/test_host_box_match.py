@@ -8,7 +8,6 @@
 * the registries build the assigner from the reference's own config block;
 * CPU tensors fail loudly, and the entry points validate their arguments before anything touches a device."""
 import importlib.util
-import inspect
 import json
 import os
 import re
@@ -110,46 +109,14 @@ def test_fixture_is_what_the_reference_computes_now(name):
             assert np.array_equal(got, want), key
 
 
-def _header_symbols():
-    with open(HEADER) as fh:
-        text = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', text)))
-
-
 def test_header_exports_and_signatures_agree():
+    """(declarations, exports and ctypes signatures: tests/test_abi_families.py)"""
     from boxinstseg_amd import _lib
     lib = _lib.load()
-    names = _header_symbols()
-    assert names, 'no declarations found'
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in boxinst_hip_assign.h but not exported'
-        assert n in _lib.ASSIGN_SIGNATURES, f'{n} has no ctypes signature'
-    assert sorted(_lib.ASSIGN_SIGNATURES) == names
-    assert not set(_lib.ASSIGN_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.POST_SIGNATURES))
-    for n, (res, args) in _lib.ASSIGN_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
     with open(HEADER) as fh:
         text = fh.read()
-    for n, (_, args) in _lib.ASSIGN_SIGNATURES.items():                       # as many parameters as the declaration has
-        decl = re.search(r'\b' + n + r'\s*\(([^)]*)\)\s*;', re.sub(r'/\*.*?\*/', '', text, flags=re.S)).group(1)
-        assert len([a for a in decl.split(',') if a.strip() and a.strip() != 'void']) == len(args), n
     assert int(re.search(r'#define BXI_MATCH_MAX_SIDE (\d+)', text).group(1)) == _lib.MATCH_MAX_SIDE
     assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
-
-
-def test_every_assign_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    from tests import test_gpu_guarded_box_match as guarded
-    for entry in _lib.ASSIGN_SIGNATURES:
-        if entry.endswith('_bytes'):
-            assert entry not in guarded.GUARDED
-            continue
-        test = guarded.GUARDED.get(entry)
-        assert test, f'{entry}: not run by a guarded test'
-        assert callable(getattr(guarded, test, None)), f'{entry}: test_gpu_guarded_box_match has no test {test}'
-        assert entry in inspect.getsource(getattr(guarded, test)), entry
-    assert not set(guarded.GUARDED) - set(_lib.ASSIGN_SIGNATURES)
 
 
 def _reference_assigner_cfg():

@@ -7,7 +7,6 @@
 import ctypes as C
 import os
 import sys
-import re
 
 import numpy as np
 import pytest
@@ -22,25 +21,10 @@ def _built(built):
     return built
 
 
-def header_symbols():
-    import glob
-    names = set()
-    for path in sorted(glob.glob(os.path.join(ROOT, 'include', '*.h'))):       # the production ABI and the developer hooks
-        src = open(path).read()
-        src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-        names |= set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', src))
-    return sorted(names - {'bxi_launch_hook'})
-
-
 def test_library_exports_every_declared_symbol():
+    """(the symbols themselves: tests/test_abi_families.py)"""
     from boxinstseg_amd import _lib
     lib = _lib.load()
-    names = header_symbols()
-    assert len(names) >= 16
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in include/boxinst_hip.h but not exported'
-        assert n in _lib.SIGNATURES, f'{n} has no ctypes signature'
-    assert sorted(_lib.SIGNATURES) == names
     assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7
     for code, name in _lib.STATUS.items():
         assert _lib.status_string(code) and 'unknown' not in _lib.status_string(code)

@@ -7,7 +7,6 @@
 * CPU tensors and bad arguments fail before any launch;
 * the test_cfg of the reference's BoxInst config, as load_config reads it, is accepted."""
 import importlib.util
-import inspect
 import json
 import os
 import re
@@ -119,21 +118,10 @@ def _header_text():
 
 
 def test_header_exports_and_signatures_agree():
+    """(declarations, exports and ctypes signatures: tests/test_abi_families.py)"""
     from boxinstseg_amd import _lib, box_nms
     lib = _lib.load()
     text = _header_text()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    names = sorted(set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)))
-    assert names, 'no declarations found'
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in boxinst_hip_det.h but not exported'
-    assert sorted(_lib.DET_SIGNATURES) == names
-    assert not set(_lib.DET_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.POST_SIGNATURES) | set(_lib.ASSIGN_SIGNATURES))
-    for n, (res, args) in _lib.DET_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        decl = re.search(r'\b' + n + r'\s*\(([^)]*)\)\s*;', code).group(1)
-        assert len([a for a in decl.split(',') if a.strip() and a.strip() != 'void']) == len(args), n
     for macro, value in (('BXI_DET_MAX_LEVELS', _lib.DET_MAX_LEVELS), ('BXI_DET_SORT_MAX', _lib.DET_SORT_MAX), ('BXI_DET_NMS_ROUND', _lib.DET_NMS_ROUND),
                          ('BXI_DET_KEEP_TILE', _lib.DET_KEEP_TILE), ('BXI_DET_ROW_TILE', _lib.DET_ROW_TILE),
                          ('BXI_DET_STATUS_OVER_CAP', _lib.DET_STATUS_OVER_CAP), ('BXI_DET_STATUS_OVER_SORT', _lib.DET_STATUS_OVER_SORT),
@@ -149,20 +137,6 @@ def test_header_exports_and_signatures_agree():
     with open(os.path.join(ROOT, 'INTEGRATION.md')) as fh:
         integration = fh.read()
     assert 'Level 3d' in integration and 'max coordinate + 1' in integration
-
-
-def test_every_det_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    from tests import test_gpu_guarded_det as guarded
-    for entry in _lib.DET_SIGNATURES:
-        if entry.endswith('_bytes'):
-            assert entry not in guarded.GUARDED
-            continue
-        test = guarded.GUARDED.get(entry)
-        assert test, f'{entry}: not run by a guarded test'
-        assert callable(getattr(guarded, test, None)), f'{entry}: test_gpu_guarded_det has no test {test}'
-        assert entry in inspect.getsource(getattr(guarded, test)), entry
-    assert not set(guarded.GUARDED) - set(_lib.DET_SIGNATURES)
 
 
 def test_reference_test_cfg_is_accepted():

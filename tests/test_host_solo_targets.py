@@ -7,7 +7,6 @@
 * the bbox_head block of every configs/discobox and configs/boxlevelset file is accepted (tests/golden/solo_head_cfg.json);
 * CPU tensors and bad arguments fail before any launch."""
 import importlib.util
-import inspect
 import json
 import os
 import re
@@ -131,23 +130,11 @@ def test_fixture_is_what_the_reference_computes_now(name):
 
 
 def test_header_exports_and_signatures_agree():
+    """(declarations, exports and ctypes signatures: tests/test_abi_families.py)"""
     from boxinstseg_amd import _lib, solo_targets
     lib = _lib.load()
     with open(HEADER) as fh:
         text = fh.read()
-    code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    names = sorted(set(re.findall(r'\b(bxi_solo_[a-z0-9_]+)\s*\(', code)))
-    assert names, 'no declarations found'
-    for n in names:
-        assert hasattr(lib, n), f'{n} declared in boxinst_hip_solo.h but not exported'
-    assert sorted(_lib.SOLO_SIGNATURES) == names
-    assert not set(_lib.SOLO_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.POST_SIGNATURES) | set(_lib.ASSIGN_SIGNATURES) | set(_lib.DET_SIGNATURES) |
-                                            set(_lib.FCOS_SIGNATURES))
-    for n, (res, args) in _lib.SOLO_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        decl = re.search(r'\b' + n + r'\s*\(([^)]*)\)\s*;', code).group(1)
-        assert len([a for a in decl.split(',') if a.strip() and a.strip() != 'void']) == len(args), n
     for macro, value in (('BXI_SOLO_MODE_DISCOBOX', _lib.SOLO_MODES['discobox']), ('BXI_SOLO_MODE_BOXLEVELSET', _lib.SOLO_MODES['boxlevelset']),
                          ('BXI_SOLO_MAX_FACTORS', _lib.SOLO_MAX_FACTORS), ('BXI_SOLO_MAX_FACTOR', _lib.SOLO_MAX_FACTOR),
                          ('BXI_SOLO_RESCALE_MIN_ONES', _lib.SOLO_RESCALE_MIN_ONES), ('BXI_SOLO_MIN_MASK_SUM', _lib.SOLO_MIN_MASK_SUM),
@@ -163,20 +150,6 @@ def test_header_exports_and_signatures_agree():
     for word in ('Level 3f', 'unpinned', 'rounded once', 'best_target_single', 'F.interpolate', 'F.conv2d', 'all-zero targets',
                  'bxi_solo_mask_pass_u8', 'bxi_solo_assign_f32', 'bxi_solo_cate_loss_f32'):
         assert word in integration, word
-
-
-def test_every_solo_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    from tests import test_gpu_guarded_solo_targets as guarded
-    for entry in _lib.SOLO_SIGNATURES:
-        if entry.endswith('_bytes'):
-            assert entry not in guarded.GUARDED
-            continue
-        test = guarded.GUARDED.get(entry)
-        assert test, f'{entry}: not run by a guarded test'
-        assert callable(getattr(guarded, test, None)), f'{entry}: test_gpu_guarded_solo_targets has no test {test}'
-        assert entry in inspect.getsource(getattr(guarded, test)), entry
-    assert set(guarded.GUARDED) == {e for e in _lib.SOLO_SIGNATURES if not e.endswith('_bytes')}
 
 
 def test_reference_head_blocks_are_accepted():
