@@ -90,7 +90,7 @@ int bxi_boxinst_targets_f32(const bxi_image_batch* batch_host, const float* cons
     if (size < 1 || (size & 1) == 0 || dilation < 1 || stride < 1) return BXI_ERR_BAD_ARGUMENT;
     if (size != 3 || !bxi::fused_eval_supported(dilation)) return BXI_ERR_UNSUPPORTED;
     const size_t need = bxi_boxinst_eval_workspace_bytes(batch_host->B, batch_host->Hc, batch_host->Wc, stride, 0);
-    if (!workspace || need == 0 || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return BXI_ERR_WORKSPACE;
+    if (need == 0 || !bxi::workspace_ok(workspace, workspace_bytes, need, 256)) return BXI_ERR_WORKSPACE;
     return bxi::launch_targets(batch_host, boxes_per_img_host, gt_count_host, stride, dilation, color_thresh, workspace, workspace_bytes, stream);
 }
 
@@ -114,7 +114,7 @@ int bxi_boxinst_eval_f32(const bxi_image_batch* batch_host, const bxi_instances*
         return BXI_ERR_BAD_SHAPE;
     const size_t need = bxi_boxinst_eval_workspace_bytes(batch_host->B, batch_host->Hc, batch_host->Wc, stride,
                                                          inst_host->N);
-    if (!workspace || need == 0 || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255))
+    if (need == 0 || !bxi::workspace_ok(workspace, workspace_bytes, need, 256))
         return BXI_ERR_WORKSPACE;
     if (bad_eval_flags(flags)) return BXI_ERR_BAD_ARGUMENT;
     return bxi::launch_fused_eval(batch_host, color_thresh, inst_host, dilation, warmup, up_prj, up_pw, losses, g_logits, state, workspace,
@@ -142,7 +142,7 @@ int bxi_boxinst_head_eval_f32(const bxi_image_batch* batch_host, const bxi_insta
                            in_stride, factor, disable_rel_coors, da);
     if (rc != BXI_OK) return rc;
     const size_t need = bxi_boxinst_eval_workspace_bytes(batch_host->B, batch_host->Hc, batch_host->Wc, stride, inst_host->N);
-    if (!workspace || need == 0 || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return BXI_ERR_WORKSPACE;
+    if (need == 0 || !bxi::workspace_ok(workspace, workspace_bytes, need, 256)) return BXI_ERR_WORKSPACE;
     return bxi::launch_fused_eval(batch_host, color_thresh, inst_host, dilation, warmup, up_prj, up_pw, losses, g_logits, state, workspace,
                                   workspace_bytes, flags, stream, &da, C);
 }

@@ -398,7 +398,7 @@ inline int proj_check(const void* src, int n, int H, int W, float* proj_rows, fl
     if (n < 0 || !plane_ok(H, W) || n > 65535) return BXI_ERR_BAD_SHAPE;
     if (n == 0) return BXI_OK;
     if (!src || !proj_rows || !proj_cols || !sumsq) return BXI_ERR_NULL_POINTER;
-    if (!ws || ws_bytes < bxi_box_match_workspace_bytes(n, H, W) || (reinterpret_cast<uintptr_t>(ws) & 3)) return BXI_ERR_WORKSPACE;
+    if (!workspace_ok(ws, ws_bytes, bxi_box_match_workspace_bytes(n, H, W), 4)) return BXI_ERR_WORKSPACE;
     return BXI_OK;
 }
 

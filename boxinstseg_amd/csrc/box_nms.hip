@@ -68,29 +68,6 @@ __global__ __launch_bounds__(256) void det_location_score_kernel(DetLevels lv, i
     loc_score[(size_t)b * m_all + loc] = __fmul_rn(sigmoidf_(mx), sigmoidf_(ctr));
 }
 
-// inclusive scan of one int over the 256 threads of a workgroup (thread order); `total` is the workgroup's sum
-__device__ __forceinline__ int block_scan_256(int v, int* s_wave /*[4]*/, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const int t = s_wave[w];
-        if (w < wave) before += t;
-        total += t;
-    }
-    __syncthreads();
-    return inc + before;
-}
-
 template <bool WRITE>
 __global__ __launch_bounds__(kCandThreads) void det_candidates_kernel(DetLevels lv, ImgDims dims, int C, const int64_t* __restrict__ sel,
                                                                       int M, int rescale, float thr, int cap, float* __restrict__ boxes,
@@ -142,10 +119,9 @@ __global__ __launch_bounds__(kCandThreads) void det_candidates_kernel(DetLevels 
     __syncthreads();
     const int base = s_base;
     int total;
-    const int inc = block_scan_256(n, s_wave, total);
+    int slot = base + block_scan_excl_i32<kCandThreads / 64>(n, s_wave, total);
     if (tile == tiles - 1 && tid == 0) count[b] = base + total;
     if (n == 0) return;
-    int slot = base + inc - n;
     if (slot >= cap) return;
 
     // the row's box (transforms.py:153-184, condinst_head.py:808-810)
@@ -497,7 +473,7 @@ extern "C" int bxi_det_candidates_f32(const bxi_det_level* levels_host, int n_le
     if (M < 0 || cap < 0 || !fits_i32((int64_t)M * C) || !fits_i32((int64_t)B * cap * 4)) return BXI_ERR_BAD_SHAPE;
     if (!(score_thr == score_thr)) return BXI_ERR_BAD_ARGUMENT;
     if (!img_dims_host || !count || (cap > 0 && (!cand_boxes || !cand_scores || !cand_labels || !cand_pos))) return BXI_ERR_NULL_POINTER;
-    if (!workspace || workspace_bytes < bxi_det_candidates_workspace_bytes(B, M) || (reinterpret_cast<uintptr_t>(workspace) & 3))
+    if (!workspace_ok(workspace, workspace_bytes, bxi_det_candidates_workspace_bytes(B, M), 4))
         return BXI_ERR_WORKSPACE;
     ImgDims dims;
     for (int b = 0; b < BXI_MAX_IMAGES; ++b)
@@ -538,7 +514,7 @@ extern "C" int bxi_box_nms_f32(const float* boxes, const float* scores, const in
     if (!boxes || !count || !keep || !n_keep || !status || (!order && !scores)) return BXI_ERR_NULL_POINTER;
     const int spill_n = nms_spill_rows(cap, max_keep);
     const bool need_ws = !order || spill_n > 0;
-    if (need_ws && (!workspace || workspace_bytes < bxi_box_nms_workspace_bytes(P, cap, max_keep) || (reinterpret_cast<uintptr_t>(workspace) & 3)))
+    if (need_ws && !workspace_ok(workspace, workspace_bytes, bxi_box_nms_workspace_bytes(P, cap, max_keep), 4))
         return BXI_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     int32_t* ws = static_cast<int32_t*>(workspace);

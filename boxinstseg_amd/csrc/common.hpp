@@ -45,6 +45,27 @@ struct LaunchScope {
 
 inline bool fits_i32(int64_t v) { return v >= 0 && v <= 0x7fffffffLL; }
 
+// A caller's buffer as an entry point accepts it: present, large enough, aligned to `align` bytes (a power of two, here and in Carver).
+inline bool aligned(const void* p, size_t align) { return !(reinterpret_cast<uintptr_t>(p) & (align - 1)); }
+inline bool workspace_ok(const void* ws, size_t have, size_t need, size_t align) { return ws && have >= need && aligned(ws, align); }
+
+// Carves consecutive arrays out of one buffer, every array starting on a multiple of `align` from the base; a null base measures only
+// (take() returns null, bytes() is the size to ask for).  The one layout rule of every workspace and `state` block of the library --
+// the *_workspace_bytes queries and the kernels that carve again on the device must agree to the byte, so there is one copy.
+// Sizes are rounded with a mask, not as x / align * align: from the division form the compiler derives x - x % align, moves the `+ align - 1`
+// into the instructions' immediate offsets and leaves base registers that are not dword-aligned -- which a scalar load (it ignores the two
+// low bits of its base AND of its offset) then reads the wrong word through.
+struct Carver {
+    char* base; size_t align, off;
+    __host__ __device__ Carver(void* b, size_t a) : base(static_cast<char*>(b)), align(a), off(0) {}
+    template <typename T> __host__ __device__ T* take(size_t count) {
+        const size_t o = off;
+        off += (sizeof(T) * count + align - 1) & ~(align - 1);
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+    __host__ __device__ size_t bytes() const { return off; }
+};
+
 // compute units of the current device (256 on an MI355X in SPX mode, 32 per partition in CPX): grids are sized so that a launch is
 // resident in one round.  Cached per device ordinal; a wrong value costs time, never correctness.
 inline int device_cus() {
@@ -180,10 +201,73 @@ __device__ __forceinline__ int first_col_of_max(float lane_max, int lane_col, fl
     const int col = wave_min_i32(mine ? lane_col : 0x7fffffff);
     return col == 0x7fffffff ? __builtin_amdgcn_readlane(lane_col, 0) : col;
 }
-// (the historical names: every kernel's wave reduction goes through the DPP forms above)
-__device__ __forceinline__ float wave_sum_f32(float v) { return wave_total_f32(v); }
-__device__ __forceinline__ double wave_sum_f64(double v) { return wave_total_f64(v); }
-__device__ __forceinline__ int wave_sum_i32(int v) { return wave_total_i32(v); }
+// Inclusive prefix sum over the 64 lanes on the DPP path: Hillis-Steele inside a row of 16 lanes (row_shr 1, 2, 4, 8; lanes without a source add 0),
+// then the rows' totals by row_bcast:15 (rows 1, 3) and row_bcast:31 (rows 2, 3).  Ten VALU instructions, no LDS.
+__device__ __forceinline__ uint32_t wave_scan_incl_u32(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111 /* row_shr:1 */, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112 /* row_shr:2 */, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114 /* row_shr:4 */, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118 /* row_shr:8 */, 0xf, 0xf, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142 /* row_bcast:15 */, 0xa, 0xf, false);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143 /* row_bcast:31 */, 0xc, 0xf, false);
+    return v;
+}
+__device__ __forceinline__ int wave_scan_incl_i32(int v) { return (int)wave_scan_incl_u32((uint32_t)v); }
+// Exclusive prefix sum of one int per thread over a workgroup of exactly WAVES waves, in thread order; `total` is the workgroup's sum
+// (every thread gets both; a caller that wants the inclusive value adds its own v).  The wave scan, the waves' totals handed over through
+// part[WAVES], then every wave scans those totals again (lane w reads wave w's) and picks the sum of the waves before it and the last one
+// by v_readlane: one LDS read and a few registers whatever WAVES is.  Called by all threads of the workgroup, every lane active.  The
+// barrier BEHIND the reads makes a second call on the same `part` safe right away; the caller sees to it that nobody still uses `part` for
+// something else when the first one starts.
+template <int WAVES>
+__device__ __forceinline__ int block_scan_excl_i32(int v, int* part /*[WAVES]*/, int& total) {
+    static_assert(WAVES >= 1 && WAVES <= 16, "a workgroup has at most 1024 threads");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int incl = wave_scan_incl_i32(v);
+    if (lane == 63) part[wave] = incl;
+    __syncthreads();
+    const int t = lane < WAVES ? part[lane] : 0;
+    const int upto = wave_scan_incl_i32(t);
+    __syncthreads();
+    total = __builtin_amdgcn_readlane(upto, WAVES - 1);
+    return __builtin_amdgcn_readlane(upto - t, __builtin_amdgcn_readfirstlane(wave)) + incl - v;
+}
+
+// ---- workgroup sums in a fixed order ---------------------------------------------------------------------------------
+// Two orders, two names: these are fp64 loss sums whose order is part of the results, so the forms are not interchangeable.
+//
+// block_sum_seq_f64: ANY number of waves (blockDim.x / 64 <= 16), the wave totals added one after the other in wave order,
+// ((w0 + w1) + w2) + ...; every thread gets the sum.  LDS: red[16] doubles.  Barriers: one BEFORE the hand-over (a second
+// call may reuse `red`: nobody still reads the previous call's totals once every wave is past it), one after it; none behind
+// the reads -- the next call's leading barrier is what protects them.
+__device__ __forceinline__ double block_sum_seq_f64(double v, double* red /*[16]*/) {
+    v = wave_total_f64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];   // fixed order
+    return s;
+}
+// block_sum_4w_f64 / block_sum_4w_i32: EXACTLY four waves (256 threads), the wave totals pairwise, (w0 + w1) + (w2 + w3); every
+// thread gets the sum.  LDS: s4[4].  Barriers: one after the hand-over and one AFTER the reads, so `s4` is free again when the
+// call returns and calls on the same `s4` may follow each other directly.
+__device__ __forceinline__ double block_sum_4w_f64(double v, double* s4) {
+    v = wave_total_f64(v);
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double r = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ int block_sum_4w_i32(int v, int* s4) {
+    v = wave_total_i32(v);
+    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int r = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+    __syncthreads();
+    return r;
+}
 
 // Workgroup barrier that orders LDS traffic only: unlike __syncthreads() it does not wait for the
 // wave's outstanding global stores (vmcnt), so zero-fill / output stores stay in flight across it.

@@ -781,7 +781,7 @@ int bxi_dynamic_mask_backward_f32(const float* feat, int B, int C, int H, int W,
     if (rc != BXI_OK) return rc;
     if (!g_feat || (N > 0 && (!g_logits || !g_params))) return BXI_ERR_NULL_POINTER;
     const size_t need = bxi_dynamic_mask_backward_workspace_bytes(B, C, H, W, N, disable_rel_coors);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return BXI_ERR_WORKSPACE;
+    if (!bxi::workspace_ok(workspace, workspace_bytes, need, 256)) return BXI_ERR_WORKSPACE;
     hipStream_t s = bxi::as_stream(stream);
     const int T = bxi::dyn_tiles(H, W), P = bxi::dyn_params(C, a.rel);
     const int64_t feat_elems = (int64_t)B * C * H * W;

@@ -337,7 +337,17 @@ static int fill_dyn_generic(const float* feat, int B, int C, int H, int W, const
 }
 
 static inline int pad_dc(int Dc) { return Dc <= 4 ? 4 : (Dc <= 8 ? 8 : 16); }
-static inline size_t gen_dy_bytes(int N, int H, int W) { return align_up(sizeof(float) * (size_t)(N > 0 ? N : 1) * H * W, 256); }
+// workspace of the backward: d loss / d (up-sampled logits) folded to the head's resolution, then the per-tile partial sums of the parameter gradients
+struct GenBwdWs { float* dy; float* part; };
+static inline size_t carve_gen_bwd(void* base, int N, int H, int W, size_t T, const GenShape& s, GenBwdWs* ws) {
+    const size_t N1 = (size_t)(N > 0 ? N : 1);
+    Carver cv(base, 256);
+    GenBwdWs t;
+    t.dy = cv.take<float>(N1 * H * W);
+    t.part = cv.take<float>(N1 * T * s.P);
+    if (ws) *ws = t;
+    return cv.bytes();
+}
 
 }  // namespace bxi
 
@@ -371,7 +381,7 @@ size_t bxi_dynamic_mask_generic_backward_workspace_bytes(int B, int C, int H, in
     (void)B;
     if (!gen_shape(layers, channels, C, !disable_rel_coors, s) || H <= 0 || W <= 0 || N < 0) return 0;
     const size_t T = (size_t)((H + kYR - 1) / kYR) * ((W + kYC - 1) / kYC);
-    return gen_dy_bytes(N, H, W) + align_up(sizeof(float) * (size_t)(N > 0 ? N : 1) * T * s.P, 256);
+    return carve_gen_bwd(nullptr, N, H, W, T, s, nullptr);
 }
 
 int bxi_dynamic_mask_generic_backward_f32(const float* feat, int B, int C, int H, int W, const float* params, int N, int layers, int channels,
@@ -388,10 +398,12 @@ int bxi_dynamic_mask_generic_backward_f32(const float* feat, int B, int C, int H
     if (B > 65535) return BXI_ERR_BAD_SHAPE;
     hipStream_t st = as_stream(stream);
     const size_t need = bxi_dynamic_mask_generic_backward_workspace_bytes(B, C, H, W, N, layers, channels, disable_rel_coors);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return BXI_ERR_WORKSPACE;
-    float* dy = reinterpret_cast<float*>(workspace);
-    float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + gen_dy_bytes(N, H, W));
+    if (!workspace_ok(workspace, workspace_bytes, need, 256)) return BXI_ERR_WORKSPACE;
     const int T = ((H + kYR - 1) / kYR) * ((W + kYC - 1) / kYC);
+    GenBwdWs gw;
+    carve_gen_bwd(workspace, N, H, W, (size_t)T, s, &gw);
+    float* dy = gw.dy;
+    float* part = gw.part;
     if (N > 0) {
         const int64_t npx = (int64_t)N * H * W;
         if (!fits_i32((npx + 255) / 256)) return BXI_ERR_BAD_SHAPE;

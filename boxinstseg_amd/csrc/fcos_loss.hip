@@ -127,8 +127,8 @@ __global__ __launch_bounds__(kLocTile) void fcos_targets_kernel(LocGrid g, Range
         img_inds[n] = b;
         ctr_targets[n] = ct;
     }
-    const int npos = block_sum_i32(pos ? 1 : 0, s4i);
-    const double csum = block_sum_f64((double)ct, s4d);
+    const int npos = block_sum_4w_i32(pos ? 1 : 0, s4i);
+    const double csum = block_sum_4w_f64((double)ct, s4d);
     if (tid == 0) {
         int32_t* p = partials + 4 * (size_t)blockIdx.x;
         const long long cbits = __double_as_longlong(csum);     // the centerness sum stays fp64 until the one final rounding
@@ -153,9 +153,9 @@ __global__ __launch_bounds__(256) void fcos_finish_kernel(const int32_t* __restr
             cs += __longlong_as_double(((long long)partials[4 * (size_t)i + 2] << 32) | (unsigned int)partials[4 * (size_t)i + 1]);
             bad |= partials[4 * (size_t)i + 3];
         }
-        np = block_sum_i32(np, s4i);
-        bad = block_sum_i32(bad ? 1 : 0, s4i);
-        cs = block_sum_f64(cs, s4d);
+        np = block_sum_4w_i32(np, s4i);
+        bad = block_sum_4w_i32(bad ? 1 : 0, s4i);
+        cs = block_sum_4w_f64(cs, s4d);
         if (tid == 0) {
             out[0] = (float)np;
             out[1] = (float)cs;
@@ -169,9 +169,9 @@ __global__ __launch_bounds__(256) void fcos_finish_kernel(const int32_t* __restr
         a1 += (double)__int_as_float(partials[4 * (size_t)i + 1]);
         a2 += (double)__int_as_float(partials[4 * (size_t)i + 2]);
     }
-    a0 = block_sum_f64(a0, s4d);
-    a1 = block_sum_f64(a1, s4d);
-    a2 = block_sum_f64(a2, s4d);
+    a0 = block_sum_4w_f64(a0, s4d);
+    a1 = block_sum_4w_f64(a1, s4d);
+    a2 = block_sum_4w_f64(a2, s4d);
     if (tid == 0) {
         out[0] = (float)a0;
         out[1] = (float)a1;
@@ -304,8 +304,8 @@ __global__ __launch_bounds__(kLocTile) void fcos_pos_kernel(Maps m, LocGrid g, i
         gb[0] = gd[0]; gb[hw] = gd[1]; gb[2 * hw] = gd[2]; gb[3 * hw] = gd[3];
         m.gctr[l][(size_t)b * hw + yx] = gc;
     }
-    const double tb = block_sum_f64((double)loss_b, s4d);
-    const double tc = block_sum_f64((double)loss_c, s4d);
+    const double tb = block_sum_4w_f64((double)loss_b, s4d);
+    const double tc = block_sum_4w_f64((double)loss_c, s4d);
     if (threadIdx.x == 0) {
         int32_t* p = partials + 4 * (size_t)(part_first + blockIdx.x);
         p[0] = 0;
@@ -364,7 +364,7 @@ extern "C" int bxi_fcos_targets_f32(const bxi_fcos_level* levels_host, int n_lev
         (off.v[B] > 0 && (!gt_boxes || !gt_labels)))
         return BXI_ERR_NULL_POINTER;
     const int n_blocks = g.blk_first[g.n];
-    if (!workspace_ok(workspace, workspace_bytes, 16 * (size_t)n_blocks)) return BXI_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, 16 * (size_t)n_blocks, 4)) return BXI_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     int32_t* part = static_cast<int32_t*>(workspace);
     BXI_LAUNCH("fcos_targets", s, fcos_targets_kernel, dim3((unsigned)n_blocks), dim3(kLocTile), 0, s, g, rg, off, center_sampling ? 1 : 0,
@@ -410,7 +410,7 @@ extern "C" int bxi_fcos_loss_f32(const bxi_det_level* levels_host, int n_levels,
     }
     const int loc_blocks = g.blk_first[g.n];
     const int n_blocks = (int)focal_blocks + loc_blocks;
-    if (!workspace_ok(workspace, workspace_bytes, 16 * (size_t)n_blocks)) return BXI_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, 16 * (size_t)n_blocks, 4)) return BXI_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     int32_t* part = static_cast<int32_t*>(workspace);
     if (gamma == 2.f)

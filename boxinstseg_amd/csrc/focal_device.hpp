@@ -1,5 +1,5 @@
 // focal_device.hpp -- what the two training-loss files share (fcos_loss.hip, solo_targets.hip): the (level, image, tile) grid of the
-// flattened training order, the flat segment grid, the fixed-order workgroup sums, the sigmoid focal loss of one logit with its
+// flattened training order, the flat segment grid, the sigmoid focal loss of one logit with its
 // derivative and of one workgroup's tile of a [B][C][HW] map, the flat rescale kernel of the backward step, and the per-image box
 // offsets as the kernels take them.  Everything sits in an unnamed namespace: each file has its own copy.
 #pragma once
@@ -42,24 +42,6 @@ struct FlatGrid {
 };
 // first box of every image, padded with the total: v[b] = gt_offsets_host[min(b, B)]
 struct GtOffsets { int v[BXI_MAX_IMAGES + 1]; };
-
-// workgroup sums in a fixed order: the DPP wave total, then the four waves pairwise (thread 0 holds the result)
-__device__ __forceinline__ double block_sum_f64(double v, double* s4) {
-    v = wave_total_f64(v);
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ int block_sum_i32(int v, int* s4) {
-    v = wave_total_i32(v);
-    if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const int r = (s4[0] + s4[1]) + (s4[2] + s4[3]);
-    __syncthreads();
-    return r;
-}
 
 // ---- focal loss -----------------------------------------------------------------------------------------------------------
 template <bool G2>
@@ -126,7 +108,7 @@ __device__ __forceinline__ double focal_tile(const float* __restrict__ src, floa
         for (int j = 0; j < 4; ++j)
             if (e0 + j < count) dst[e0 + j] = gr[j];
     }
-    return block_sum_f64((double)sum, s4d);
+    return block_sum_4w_f64((double)sum, s4d);
 }
 
 // ---- backward rescale -----------------------------------------------------------------------------------------------------
@@ -215,8 +197,6 @@ int read_offsets(const int* gt_offsets_host, int B, GtOffsets& off) {
     }
     return BXI_OK;
 }
-
-bool workspace_ok(const void* ws, size_t have, size_t need) { return ws && have >= need && !(reinterpret_cast<uintptr_t>(ws) & 3); }
 
 }  // namespace
 }  // namespace bxi

@@ -17,16 +17,6 @@ namespace bxi {
 
 constexpr int kLsMaxC = 8;        // target channels a launch of the partial sums keeps in registers; more channels = more launches (groups of 8)
 
-__device__ __forceinline__ double block_sum_f64_ls(double v, double* red /*[16]*/) {
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];   // fixed order
-    return s;
-}
-
 // state per instance: S[2] | a[2][C] | R[2][C]   (doubles; R = A - a S, zero unless the clamp of :34-35 is active),
 // followed (after all instances) by the partial sums of the slices: [N][kLsSlices][2 + 4C]  = S[2] | A[2][C] | Q[2][C]
 __device__ __forceinline__ int ls_stride(int C) { return 2 + 4 * C; }
@@ -107,12 +97,12 @@ __global__ __launch_bounds__(kLsThreads) void levelset_partial_kernel(const floa
     // thread q adds the 16 wave partials of sum q in wave order -- the same additions in the same order as before.
     double* part = state + (int64_t)N * ls_stride(C) + ((int64_t)n * kLsSlices + sl) * ls_stride(C);
     const int n_sums = ls_stride(Cg);
-    S[0] = wave_sum_f64(S[0]); S[1] = wave_sum_f64(S[1]);
+    S[0] = wave_total_f64(S[0]); S[1] = wave_total_f64(S[1]);
 #pragma unroll
     for (int c = 0; c < kLsMaxC; ++c)
         if (c < Cg) {
-            A[0][c] = wave_sum_f64(A[0][c]); A[1][c] = wave_sum_f64(A[1][c]);
-            Q[0][c] = wave_sum_f64(Q[0][c]); Q[1][c] = wave_sum_f64(Q[1][c]);
+            A[0][c] = wave_total_f64(A[0][c]); A[1][c] = wave_total_f64(A[1][c]);
+            Q[0][c] = wave_total_f64(Q[0][c]); Q[1][c] = wave_total_f64(Q[1][c]);
         }
     if ((tid & 63) == 0) {
         double* r = red + (tid >> 6) * (2 + 4 * kLsMaxC);
@@ -618,7 +608,7 @@ int bxi_levelset_loss_forward_f32(const float* mask_score, const float* target, 
     if (N == 0) return BXI_OK;
     if (!mask_score || !target || !pixel_num || !loss || !state) return BXI_ERR_NULL_POINTER;
     if (!bxi::fits_i32((int64_t)N * H * W * (C > 2 ? C : 2))) return BXI_ERR_BAD_SHAPE;
-    if (reinterpret_cast<uintptr_t>(state) & 7) return BXI_ERR_WORKSPACE;
+    if (!bxi::aligned(state, 8)) return BXI_ERR_WORKSPACE;
     hipStream_t s = bxi::as_stream(stream);
     if (N > 65535) return BXI_ERR_UNSUPPORTED;
     const bool vec = ((int64_t)H * W) % 4 == 0 && ((reinterpret_cast<uintptr_t>(mask_score) | reinterpret_cast<uintptr_t>(target)) & 15) == 0;
@@ -733,7 +723,7 @@ int bxi_lcm_refine_f32(const float* aff, const float* phi, int N, int h, int w, 
         }
     }
     // large maps: ping-pong between `out` and the workspace plane, one launch per iteration
-    if (!workspace || workspace_bytes < bxi_lcm_workspace_bytes(N, h, w) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+    if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_lcm_workspace_bytes(N, h, w), 16))
         return BXI_ERR_WORKSPACE;
     const int64_t total = (int64_t)N * h * w;
     if (iters == 0) {

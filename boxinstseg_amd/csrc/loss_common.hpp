@@ -40,25 +40,22 @@ struct LossState {            // what the backward / rescale entry points need (
     float* iter;              // bxi_instances.iter_counter (not part of `state`): + 1.0f by the evaluation's finisher
 };
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 static inline size_t carve_state(void* base, int N, int h, int w, LossState* st) {
-    size_t off = 0;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return p ? p + o : nullptr; };
-    int* colarg = (int*)take(sizeof(int) * (size_t)N * w);
-    int* rowarg = (int*)take(sizeof(int) * (size_t)N * h);
-    float* gcol = (float*)take(sizeof(float) * (size_t)N * w);
-    float* grow = (float*)take(sizeof(float) * (size_t)N * h);
-    InstRec* inst = (InstRec*)take(32 * (size_t)(N > 0 ? N : 1));
-    float* scale = (float*)take(2 * sizeof(float));     // [0] warmup / max(sum W, 1); [1] the warm-up factor itself (fused_eval.hip)
-    float* applied = (float*)take(2 * sizeof(float));
-    unsigned long long* colk = (unsigned long long*)take(8 * (size_t)N * w);
-    unsigned long long* rowk = (unsigned long long*)take(8 * (size_t)N * h);
-    int* status = (int*)take(2 * sizeof(int));
+    Carver cv(base, 256);
+    static_assert(sizeof(InstRec) == 32, "one 32-byte load per workgroup; part of the `state` layout");
+    int* colarg = cv.take<int>((size_t)N * w);
+    int* rowarg = cv.take<int>((size_t)N * h);
+    float* gcol = cv.take<float>((size_t)N * w);
+    float* grow = cv.take<float>((size_t)N * h);
+    InstRec* inst = cv.take<InstRec>((size_t)(N > 0 ? N : 1));
+    float* scale = cv.take<float>(2);     // [0] warmup / max(sum W, 1); [1] the warm-up factor itself (fused_eval.hip)
+    float* applied = cv.take<float>(2);
+    unsigned long long* colk = cv.take<unsigned long long>((size_t)N * w);
+    unsigned long long* rowk = cv.take<unsigned long long>((size_t)N * h);
+    int* status = cv.take<int>(2);
     if (st) { st->colarg = colarg; st->rowarg = rowarg; st->gcol = gcol; st->grow = grow; st->inst = inst; st->scale = scale;
               st->applied = applied; st->colk = colk; st->rowk = rowk; st->status = status; }
-    return off;
+    return cv.bytes();
 }
 
 // ---- device helpers ----------------------------------------------------------------------------
@@ -106,6 +103,21 @@ __device__ __forceinline__ float2 sig_pair(float x) {
     const float r = __builtin_amdgcn_rcpf(1.f + e);   // v_rcp_f32 (1 ulp); __frcp_rn would expand to a full IEEE division
     const float er = e * r;
     return x >= 0.f ? make_float2(r, er) : make_float2(er, r);
+}
+
+// the leader workgroups' sigmoid (1 / (1 + exp(-x)) as the reference computes it) and their four sums at once: 256 threads, the four
+// wave totals pairwise; red[16], a barrier before and after the hand-over, none behind the reads
+__device__ __forceinline__ float sigmoid_acc(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ void block_sum4(float (&v)[4], float* red /*[16]*/) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = wave_total_f32(v[k]);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) red[(threadIdx.x >> 6) * 4 + k] = v[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = (red[k] + red[4 + k]) + (red[8 + k] + red[12 + k]);
 }
 
 __device__ __forceinline__ float4 load4(const float* row, int c, int w, bool vec) {

@@ -46,22 +46,21 @@ static inline int box_tiles(int h, int w) { return ((h + kBR - 1) / kBR) * ((w +
 
 static size_t carve_ws(void* base, int N, int h, int w, LossWs* ws) {
     const size_t T = (size_t)stream_tiles(h);
-    size_t off = 0;
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return p ? p + o : nullptr; };
-    unsigned long long* colkey = (unsigned long long*)take(sizeof(unsigned long long) * N * T * w);
-    unsigned long long* rowkey = (unsigned long long*)take(sizeof(unsigned long long) * (size_t)N * h);
-    unsigned long long* acc = (unsigned long long*)take(sizeof(unsigned long long) * 2 * (size_t)(N > 0 ? N : 1));
-    InstRec* inst = (InstRec*)take(sizeof(InstRec) * (size_t)(N > 0 ? N : 1));
-    WorkRec* work = (WorkRec*)take(sizeof(WorkRec) * (size_t)(N > 0 ? N : 1) * (size_t)box_tiles(h, w));
-    int* nwork = (int*)take(sizeof(int));
-    unsigned int* arrive = (unsigned int*)take(sizeof(unsigned int) * (size_t)(N + 1));
-    unsigned int* expect = (unsigned int*)take(sizeof(unsigned int) * (size_t)(N > 0 ? N : 1));
-    float* dice = (float*)take(sizeof(float) * (size_t)(N > 0 ? N : 1));
+    const size_t N1 = (size_t)(N > 0 ? N : 1);
+    Carver cv(base, 256);
+    unsigned long long* colkey = cv.take<unsigned long long>((size_t)N * T * w);
+    unsigned long long* rowkey = cv.take<unsigned long long>((size_t)N * h);
+    unsigned long long* acc = cv.take<unsigned long long>(2 * N1);
+    InstRec* inst = cv.take<InstRec>(N1);
+    WorkRec* work = cv.take<WorkRec>(N1 * (size_t)box_tiles(h, w));
+    int* nwork = cv.take<int>(1);
+    unsigned int* arrive = cv.take<unsigned int>((size_t)(N + 1));
+    unsigned int* expect = cv.take<unsigned int>(N1);
+    float* dice = cv.take<float>(N1);
     if (ws) { ws->colkey = colkey; ws->rowkey = rowkey; ws->acc = acc; ws->inst = inst;
               ws->work = work; ws->nwork = nwork; ws->arrive = arrive; ws->expect = expect;
               ws->dice = dice; }
-    return off;
+    return cv.bytes();
 }
 
 
@@ -104,12 +103,7 @@ __device__ __forceinline__ void build_work_list(const InstArgs& a, int dil, cons
         LaneBox lb = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         if (m < a.N) lb = lane_box(a, dil, m);
         const int cm = lb.ntr * lb.ntc;
-        int incl = cm;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
+        const int incl = wave_scan_incl_i32(cm);
         if (n >= m0 && n < m0 + 64) {
             const int src = n - m0;
             base = total + __shfl(incl - cm, src, 64);
@@ -276,19 +270,6 @@ __global__ __launch_bounds__(64) void stage1_kernel(InstArgs a, int dil, LossWs 
 //      (gather form: no atomics on the gradient, fixed summation order);
 //   3. writes the UN-normalised pairwise gradient of the whole tile (zeros outside the dilated box)
 //      and adds its integer partial sums to the instance's accumulators.
-__device__ __forceinline__ void block_sum4(float (&v)[4], float* red /*[16]*/) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = wave_sum_f32(v[k]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) red[(threadIdx.x >> 6) * 4 + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = (red[k] + red[4 + k]) + (red[8 + k] + red[12 + k]);
-}
-
-__device__ __forceinline__ float sigmoid_acc(float x) { return 1.f / (1.f + expf(-x)); }
 
 // Arrival protocol (hierarchical ticket).  Every working workgroup of box_kernel -- the box tiles and
 // the leader of an instance -- calls this once, after thread 0 has issued its agent-scope
@@ -322,8 +303,8 @@ __device__ __forceinline__ void arrive_and_finish(const LossWs& ws, const LossSt
             s = (long long)__hip_atomic_load(&ws.acc[2 * i + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             dv = __hip_atomic_load(&ws.dice[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        cnt += wave_sum_f64((double)c);                 // exact: integers far below 2^53
-        num += wave_sum_f64((double)s);
+        cnt += wave_total_f64((double)c);                 // exact: integers far below 2^53
+        num += wave_total_f64((double)s);
         const int m = min(64, N - base);
         for (int k = 0; k < m; ++k) dsum += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), k));   // index order
     }
@@ -579,8 +560,8 @@ __device__ __forceinline__ void box_body(const InstArgs& a, const uint8_t* __res
         }
         BXI_T(1, blockIdx.x, 4);
         // ---- per-instance accumulators: integers, so the result does not depend on the arrival order --------
-        num = wave_sum_f32(num);
-        cnt = wave_sum_i32(cnt);
+        num = wave_total_f32(num);
+        cnt = wave_total_i32(cnt);
         if ((tid & 63) == 0) { red[tid >> 6] = num; rcnt[tid >> 6] = cnt; }
         __syncthreads();
         if (tid == 0) {
@@ -742,12 +723,12 @@ int launch_loss(const bxi_instances* in, const uint8_t* affinity, int size, int 
     if (!affinity) return BXI_ERR_NULL_POINTER;
     if (a.N > 65535) return BXI_ERR_BAD_SHAPE;
     const size_t need = carve_ws(nullptr, a.N, a.h, a.w, nullptr);
-    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 255)) return BXI_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, need, 256)) return BXI_ERR_WORKSPACE;
     LossWs ws;
     carve_ws(workspace, a.N, a.h, a.w, &ws);
     LossState st = {};
     if (state) {
-        if (reinterpret_cast<uintptr_t>(state) & 255) return BXI_ERR_WORKSPACE;
+        if (!aligned(state, 256)) return BXI_ERR_WORKSPACE;
         carve_state(state, a.N, a.h, a.w, &st);
     }
     const int vec = ((a.w & 3) == 0 && (reinterpret_cast<uintptr_t>(a.logits) & 15) == 0 &&
@@ -786,7 +767,7 @@ int launch_backward(const bxi_instances* in, const float* g_prj, const float* g_
     if (a.N == 0) return BXI_OK;
     if (!g_prj || !g_pw || !state || !g_logits) return BXI_ERR_NULL_POINTER;
     if (a.N > 65535) return BXI_ERR_BAD_SHAPE;
-    if (reinterpret_cast<uintptr_t>(state) & 255) return BXI_ERR_WORKSPACE;
+    if (!aligned(state, 256)) return BXI_ERR_WORKSPACE;
     LossState st;
     carve_state(const_cast<void*>(state), a.N, a.h, a.w, &st);
     const size_t lds_d = (sizeof(float) + sizeof(int)) * (size_t)(a.h + a.w);

@@ -277,7 +277,7 @@ extern "C" int bxi_matrix_nms_f32(const uint64_t* bits, const int32_t* area, con
     if (n < 1 || n > BXI_NMS_MAX_CANDIDATES) return BXI_ERR_UNSUPPORTED;
     if ((kernel != BXI_NMS_KERNEL_GAUSSIAN && kernel != BXI_NMS_KERNEL_LINEAR) || !(sigma == sigma)) return BXI_ERR_BAD_ARGUMENT;
     if (!bits || !area || !labels || !order || !scores_sorted || !decayed || !decay_iou) return BXI_ERR_NULL_POINTER;
-    if (!workspace || workspace_bytes < bxi_matrix_nms_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 3)) return BXI_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, bxi_matrix_nms_workspace_bytes(n), 4)) return BXI_ERR_WORKSPACE;
     const int nwords = (h * w + 63) / 64, T = nms_tiles(n);
     float* compensate = reinterpret_cast<float*>(workspace);
     float* part = compensate + n;

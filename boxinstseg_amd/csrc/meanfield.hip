@@ -217,7 +217,7 @@ __global__ __launch_bounds__(64) void mf_valid_kernel(MfArgs a) {
     const u64* st = a.sa + (int64_t)n * total;
     int cnt = 0;
     for (int i = lane; i < total; i += 64) cnt += __popcll(st[i]);
-    cnt = wave_sum_i32(cnt);
+    cnt = wave_total_i32(cnt);
     if (lane == 0) {
         const float count = (float)cnt;
         a.valid[n] = (count >= a.vlo && count <= a.vhi) ? 1.f : 0.f;
@@ -230,16 +230,6 @@ __device__ __forceinline__ float load_t(const void* t, int u8, int64_t o) {
     return u8 ? (float)reinterpret_cast<const uint8_t*>(t)[o] : reinterpret_cast<const float*>(t)[o];
 }
 
-__device__ __forceinline__ double block_sum_f64(double v, double* red /*[16]*/) {
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];   // fixed order
-    return s;
-}
-
 __global__ __launch_bounds__(1024) void dice_fwd_kernel(const float* __restrict__ in, const void* __restrict__ tg, int t_u8,
                                                         int64_t L, float* __restrict__ loss, float* __restrict__ sums) {
     __shared__ double red[16];
@@ -249,8 +239,8 @@ __global__ __launch_bounds__(1024) void dice_fwd_kernel(const float* __restrict_
         const float i = in[(int64_t)n * L + j], t = load_t(tg, t_u8, (int64_t)n * L + j);
         a += (double)i * t; bc += (double)i * i + (double)t * t;
     }
-    a = block_sum_f64(a, red);
-    bc = block_sum_f64(bc, red) + 0.002;
+    a = block_sum_seq_f64(a, red);
+    bc = block_sum_seq_f64(bc, red) + 0.002;
     if (threadIdx.x == 0) {
         loss[n] = (float)(1.0 - 2.0 * a / bc);
         sums[2 * n] = (float)a; sums[2 * n + 1] = (float)bc;
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(256) void mil_finish_kernel(int H, int W, int nb, d
     }
     for (int r = tid; r < H; r += 256) { ar += (double)rowv[r] * rowt[r]; bcr += (double)rowv[r] * rowv[r] + (double)rowt[r] * rowt[r]; }
     // the four sums together (one after another each costs six dependent cross-lane steps and two barriers)
-    ac = wave_sum_f64(ac); bcc = wave_sum_f64(bcc); ar = wave_sum_f64(ar); bcr = wave_sum_f64(bcr);
+    ac = wave_total_f64(ac); bcc = wave_total_f64(bcc); ar = wave_total_f64(ar); bcr = wave_total_f64(bcr);
     if (lane == 0) { red[wave * 4 + 0] = ac; red[wave * 4 + 1] = bcc; red[wave * 4 + 2] = ar; red[wave * 4 + 3] = bcr; }
     __syncthreads();
     ac = bcc = ar = bcr = 0.0;
@@ -459,7 +449,7 @@ int bxi_meanfield_forward_f32(const float* kernel, int B, int H, int W, int ksiz
     if (N > 65535) return BXI_ERR_UNSUPPORTED;
     if (!kernel || !x || !targets || !ret || !valid) return BXI_ERR_NULL_POINTER;
     if (!bxi::fits_i32((int64_t)N * H * W) || !bxi::fits_i32((int64_t)B * H * W * ksize * ksize)) return BXI_ERR_BAD_SHAPE;
-    if (!workspace || workspace_bytes < bxi_meanfield_workspace_bytes(N, H, W) || (reinterpret_cast<uintptr_t>(workspace) & 7))
+    if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_meanfield_workspace_bytes(N, H, W), 8))
         return BXI_ERR_WORKSPACE;
     bxi::MfArgs a;
     a.K = kernel; a.x = x; a.t = targets; a.img = img_inds; a.inter = inter_img_mask; a.ret = ret; a.valid = valid;
@@ -534,7 +524,7 @@ static int launch_mil_fwd(const float* input, const void* target, int target_u8,
     if (N == 0) return BXI_OK;
     if (!input || !target || !loss || !state) return BXI_ERR_NULL_POINTER;
     if (!bxi::fits_i32((int64_t)N * H * W)) return BXI_ERR_BAD_SHAPE;
-    if (reinterpret_cast<uintptr_t>(state) & 15) return BXI_ERR_WORKSPACE;
+    if (!bxi::aligned(state, 16)) return BXI_ERR_WORKSPACE;
     const size_t lds = (size_t)W * 12;
     if (lds > 64 * 1024 || N > 65535) return BXI_ERR_UNSUPPORTED;
     hipStream_t s = bxi::as_stream(stream);

@@ -143,23 +143,6 @@ struct AssignCfg {
     float sigma;
 };
 
-// exclusive workgroup scan of one int per thread (Hillis-Steele through LDS); `total` is the sum of all 256
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int& total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {
-        const int t = tid >= d ? sh[tid - d] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const int incl = sh[tid];
-    total = sh[255];
-    __syncthreads();
-    return incl - v;
-}
-
 __global__ __launch_bounds__(256) void solo_assign_kernel(AssignCfg cf, GtOffsets off, const float* __restrict__ gt_boxes,
                                                           const int64_t* __restrict__ gt_labels, const long long* __restrict__ moments,
                                                           int64_t* __restrict__ cate_labels, uint8_t* __restrict__ ins_ind,
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(256) void solo_assign_kernel(AssignCfg cf, GtOffset
                                                           int32_t* __restrict__ counts, int32_t* __restrict__ num_ins,
                                                           int32_t* __restrict__ status) {
     __shared__ int owner[kMaxGrid * kMaxGrid];
-    __shared__ int scan[256];
+    __shared__ int scan[4];
     __shared__ int s_bad;
     const int tid = threadIdx.x;
     const int l = blockIdx.x / cf.B, b = blockIdx.x - l * cf.B;
@@ -230,7 +213,7 @@ __global__ __launch_bounds__(256) void solo_assign_kernel(AssignCfg cf, GtOffset
         const int rows = down - top + 1, cols = right - left + 1;
         const int cnt = (rows > 0 && cols > 0) ? rows * cols : 0;
         int total;
-        const int at = base + block_excl_scan(cnt, scan, total);
+        const int at = base + block_scan_excl_i32<4>(cnt, scan, total);
         if (cnt > 0) {
             int k = 0;
             for (int y = top; y <= down; ++y)
@@ -255,7 +238,7 @@ __global__ __launch_bounds__(256) void solo_assign_kernel(AssignCfg cf, GtOffset
         const int c = c0 + tid;
         const int own = c < cells ? owner[c] : -1;
         int total;
-        const int at = nset + block_excl_scan(own >= 0 ? 1 : 0, scan, total);
+        const int at = nset + block_scan_excl_i32<4>(own >= 0 ? 1 : 0, scan, total);
         if (c < cells) {
             cate_labels[row0 + c] = own >= 0 ? gt_labels[g0 + own] : (int64_t)cf.num_classes;
             ins_ind[row0 + c] = own >= 0 ? 1 : 0;
@@ -304,7 +287,7 @@ __global__ __launch_bounds__(256) void solo_cate_finish_kernel(const int32_t* __
     double a = 0.0;
     for (int i = threadIdx.x; i < n_blocks; i += 256)
         a += __longlong_as_double(((long long)partials[2 * (size_t)i + 1] << 32) | (unsigned int)partials[2 * (size_t)i]);
-    a = block_sum_f64(a, s4d);
+    a = block_sum_4w_f64(a, s4d);
     if (threadIdx.x == 0) out[0] = (float)a;
 }
 
@@ -454,7 +437,7 @@ extern "C" int bxi_solo_cate_loss_f32(const float* const* cate_preds_host, const
             m.cls[l] = cate_preds_host[l]; m.gcls[l] = grads_host[l];
         }
     }
-    if (!workspace_ok(workspace, workspace_bytes, 8 * (size_t)blocks)) return BXI_ERR_WORKSPACE;
+    if (!workspace_ok(workspace, workspace_bytes, 8 * (size_t)blocks, 4)) return BXI_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     int32_t* part = static_cast<int32_t*>(workspace);
     if (gamma == 2.f)

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(1024) void mst_kernel(const int* __restrict__ edge_
     u16* comp = reinterpret_cast<u16*>(best + V);                         // [V] component (= root vertex) of a vertex
     u16* link = comp + V;                                                 // [V] hook of a root
     uint32_t* chosen = reinterpret_cast<uint32_t*>(link + V);             // [ceil(E/32)] bitmap of tree edges (8V + 4V bytes in: aligned)
-    __shared__ int flag, scan[17];
+    __shared__ int flag, scan[16];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int* idx = edge_index + (int64_t)b * E * 2;
     const float* wt = edge_weight + (int64_t)b * E;
@@ -102,15 +102,8 @@ __global__ __launch_bounds__(1024) void mst_kernel(const int* __restrict__ edge_
     const int w0 = min(tid * per, nwords), w1 = min(w0 + per, nwords);
     int cnt = 0;
     for (int i = w0; i < w1; ++i) cnt += __popc(chosen[i]);
-    const int lane = tid & 63, wave = tid >> 6;
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, kWave); if (lane >= off) incl += o; }
-    if (lane == 63) scan[wave] = incl;
-    __syncthreads();
-    if (tid == 0) { int s = 0; for (int i = 0; i < 16; ++i) { const int t = scan[i]; scan[i] = s; s += t; } scan[16] = s; }
-    __syncthreads();
-    int pos = scan[wave] + incl - cnt;
+    int total;
+    int pos = block_scan_excl_i32<16>(cnt, scan, total);
     int* out = edge_out + (int64_t)b * (V - 1) * 2;
     for (int i = w0; i < w1; ++i) {
         uint32_t m = chosen[i];
@@ -121,7 +114,7 @@ __global__ __launch_bounds__(1024) void mst_kernel(const int* __restrict__ edge_
             ++pos;
         }
     }
-    if (tid == 0) n_out[b] = scan[16];
+    if (tid == 0) n_out[b] = total;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -531,7 +524,7 @@ int bxi_mst_forward_i32(const int* edge_index, const float* edge_weight, int B, 
     if (V > bxi::kTfMaxVLarge || E > 8 * bxi::kTfMaxVLarge) return BXI_ERR_UNSUPPORTED;
     if (B == 0) return BXI_OK;
     if (!edge_index || !edge_weight || !edge_out) return BXI_ERR_NULL_POINTER;
-    if (!workspace || workspace_bytes < bxi_mst_workspace_bytes(B, E, V) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return BXI_ERR_WORKSPACE;
+    if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_mst_workspace_bytes(B, E, V), 16)) return BXI_ERR_WORKSPACE;
     hipStream_t s = bxi::as_stream(stream);
     const size_t lds = (size_t)V * 12 + 4 * (size_t)((E + 31) / 32) + 16;
     if (!bxi::tf_fits_lds(V) || E > 8 * bxi::kTfMaxV || lds > 150 * 1024) {        // arrays in the workspace instead of LDS
@@ -560,7 +553,7 @@ int bxi_bfs_forward_i32(const int* tree_edges, int B, int V, int max_adj, int* s
     if (!tree_edges || !sorted_index || !sorted_parent || !sorted_child || !levels) return BXI_ERR_NULL_POINTER;
     hipStream_t s = bxi::as_stream(stream);
     if (!bxi::tf_fits_lds(V)) {
-        if (!workspace || workspace_bytes < bxi_bfs_workspace_bytes(B, V) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return BXI_ERR_WORKSPACE;
+        if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_bfs_workspace_bytes(B, V), 16)) return BXI_ERR_WORKSPACE;
         return bxi::launch_bfs_large(tree_edges, B, V, max_adj, sorted_index, sorted_parent, sorted_child, levels,
                                      reinterpret_cast<char*>(workspace), s);
     }
@@ -587,7 +580,7 @@ static int launch_refine(bxi::RefineArgs& a, void* workspace, size_t workspace_b
     for (int q = 0; q < a.n_planes; ++q)
         if (q + 1 == a.n_planes && !a.pl[q].in) return BXI_ERR_NULL_POINTER;
     if (!bxi::tf_fits_lds(a.V)) {
-        if (!workspace || workspace_bytes < bxi_tree_refine_workspace_bytes(a.B, a.C, a.V) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_tree_refine_workspace_bytes(a.B, a.C, a.V), 16))
             return BXI_ERR_WORKSPACE;
         return bxi::launch_refine_large(a.pl, a.edge_weight, a.sorted_index, a.sorted_child, a.levels, a.out_vertex, a.B, a.C, a.V, a.max_adj,
                                         a.n_planes, reinterpret_cast<char*>(workspace), bxi::as_stream(stream));
@@ -642,7 +635,7 @@ int bxi_tree_refine_backward_weight_f32(const float* grad_out, const float* edge
     if (B == 0) return BXI_OK;
     if (!grad_out || !sorted_parent || !feature_out || !feature_aggr || !feature_aggr_up || !weight_sum || !weight_sum_up || !grad_weight)
         return BXI_ERR_NULL_POINTER;
-    if (!workspace || workspace_bytes < bxi_tree_refine_backward_weight_workspace_bytes(B, C, V) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+    if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_tree_refine_backward_weight_workspace_bytes(B, C, V), 16))
         return BXI_ERR_WORKSPACE;
     char* refine_ws = reinterpret_cast<char*>(workspace) + (sizeof(float) * 4 * (size_t)B * C * V + 15) / 16 * 16;
     const size_t plane = (size_t)B * C * V;

@@ -22,19 +22,16 @@ namespace bxi {
 typedef unsigned long long u64;
 constexpr int kLT = 1024;
 
-__host__ __device__ static inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
 // ---------------------------------------------------------------------------------------------------
 struct MstLargeWs { u64* best; uint32_t* comp; uint32_t* link; uint32_t* chosen; int* act; };   // act[r]: an edge was offered in round r (r < 32); act[32]: the tree is complete
 __host__ __device__ static size_t carve_mst_large(char* base, int E, int V, MstLargeWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off += up16(b); return base ? base + o : nullptr; };
+    Carver cv(base, 16);
     MstLargeWs t;
-    t.best = (u64*)take(8 * (size_t)V); t.comp = (uint32_t*)take(4 * (size_t)V); t.link = (uint32_t*)take(4 * (size_t)V);
-    t.chosen = (uint32_t*)take(4 * (size_t)((E + 31) / 32));
-    t.act = (int*)take(4 * 33);
+    t.best = cv.take<u64>((size_t)V); t.comp = cv.take<uint32_t>((size_t)V); t.link = cv.take<uint32_t>((size_t)V);
+    t.chosen = cv.take<uint32_t>((size_t)((E + 31) / 32));
+    t.act = cv.take<int>(33);
     if (w) *w = t;
-    return off;
+    return cv.bytes();
 }
 size_t mst_large_ws_bytes(int E, int V) { return carve_mst_large(nullptr, E, V, nullptr); }
 
@@ -140,7 +137,7 @@ __global__ __launch_bounds__(256) void mstL_relabel_kernel(int E, int V, char* w
 // tree edges in ascending edge order: (1) exclusive prefix of the bitmap words' popcounts (one workgroup per graph: a few thousand
 // words), (2) a thread per word writes its edges at its prefix
 __global__ __launch_bounds__(kLT) void mstL_scan_kernel(int E, int V, int* __restrict__ n_out, char* ws_base, size_t ws_stride) {
-    __shared__ int scan[17];
+    __shared__ int scan[kLT / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     const MstLargeWs w = mst_ws(ws_base, ws_stride, b, E, V);
     const int nwords = (E + 31) / 32;
@@ -148,18 +145,11 @@ __global__ __launch_bounds__(kLT) void mstL_scan_kernel(int E, int V, int* __res
     const int w0 = min(tid * per, nwords), w1 = min(w0 + per, nwords);
     int cnt = 0;
     for (int i = w0; i < w1; ++i) cnt += __popc(w.chosen[i]);
-    const int lane = tid & 63, wave = tid >> 6;
-    int incl = cnt;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, kWave); if (lane >= off) incl += o; }
-    if (lane == 63) scan[wave] = incl;
-    __syncthreads();
-    if (tid == 0) { int s = 0; for (int i = 0; i < 16; ++i) { const int t = scan[i]; scan[i] = s; s += t; } scan[16] = s; }
-    __syncthreads();
-    int pos = scan[wave] + incl - cnt;
+    int total;
+    int pos = block_scan_excl_i32<kLT / 64>(cnt, scan, total);
     uint32_t* pre = w.link;                               // the links are done with: the words' prefixes live there (nwords <= V)
     for (int i = w0; i < w1; ++i) { pre[i] = (uint32_t)pos; pos += __popc(w.chosen[i]); }
-    if (tid == 0) n_out[b] = scan[16];
+    if (tid == 0) n_out[b] = total;
 }
 __global__ __launch_bounds__(256) void mstL_emit_kernel(const int* __restrict__ edge_index, int E, int V, int* __restrict__ edge_out, char* ws_base,
                                                         size_t ws_stride) {
@@ -212,40 +202,23 @@ struct BfsLargeWs {
 constexpr int kEulerMaxV = (1 << 20) - 1;          // arc ids (and the end marker 4V) < 2^22 and counts < 2^21 share one 64-bit word
 constexpr int kSortTile = 1024, kSortBits = 9, kSortBuckets = 1 << kSortBits;
 __host__ __device__ static size_t carve_bfs_large(char* base, int V, BfsLargeWs* w) {
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off += up16(b); return base ? base + o : nullptr; };
+    Carver cv(base, 16);
     BfsLargeWs t;
-    t.adj = (uint32_t*)take(16 * (size_t)V); t.deg = (uint32_t*)take(4 * (size_t)V); t.nodev = (uint32_t*)take(4 * (size_t)(V + 1));
-    t.nodep = (uint32_t*)take(4 * (size_t)(V + 1)); t.pos_of = (uint32_t*)take(4 * (size_t)V);
-    t.flag = (int*)take(4); t.nf = (int*)take(4); t.gw = (int*)take(4); t.gmask = (unsigned char*)take((size_t)V);
-    const bool euler = V <= kEulerMaxV;
+    t.adj = cv.take<uint32_t>(4 * (size_t)V); t.deg = cv.take<uint32_t>((size_t)V); t.nodev = cv.take<uint32_t>((size_t)(V + 1));
+    t.nodep = cv.take<uint32_t>((size_t)(V + 1)); t.pos_of = cv.take<uint32_t>((size_t)V);
+    t.flag = cv.take<int>(1); t.nf = cv.take<int>(1); t.gw = cv.take<int>(1); t.gmask = cv.take<unsigned char>((size_t)V);
+    const size_t Ve = V <= kEulerMaxV ? (size_t)V : 0;        // the Euler-tour arrays: nothing beyond kEulerMaxV vertices
     const size_t nblk = ((size_t)V + kSortTile - 1) / kSortTile;
-    t.e1 = (unsigned long long*)take(euler ? 32 * (size_t)V : 0); t.e2 = (unsigned long long*)take(euler ? 32 * (size_t)V : 0);
-    t.pk = (int*)take(euler ? 4 * (size_t)V : 0);
-    t.key0 = (uint32_t*)take(euler ? 4 * (size_t)V : 0); t.val0 = (uint32_t*)take(euler ? 4 * (size_t)V : 0);
-    t.key1 = (uint32_t*)take(euler ? 4 * (size_t)V : 0); t.val1 = (uint32_t*)take(euler ? 4 * (size_t)V : 0);
-    t.hist = (uint32_t*)take(euler ? 4 * (size_t)kSortBuckets * (nblk + 1) : 0);       // [tile][bucket], then the buckets' bases
-    t.bad = (int*)take(4);
+    t.e1 = cv.take<unsigned long long>(4 * Ve); t.e2 = cv.take<unsigned long long>(4 * Ve);
+    t.pk = cv.take<int>(Ve);
+    t.key0 = cv.take<uint32_t>(Ve); t.val0 = cv.take<uint32_t>(Ve);
+    t.key1 = cv.take<uint32_t>(Ve); t.val1 = cv.take<uint32_t>(Ve);
+    t.hist = cv.take<uint32_t>(Ve ? (size_t)kSortBuckets * (nblk + 1) : 0);       // [tile][bucket], then the buckets' bases
+    t.bad = cv.take<int>(1);
     if (w) *w = t;
-    return off;
+    return cv.bytes();
 }
 size_t bfs_large_ws_bytes(int V) { return carve_bfs_large(nullptr, V, nullptr); }
-
-// block-wide exclusive prefix sum of a small per-thread count (0..4); returns the total through `total`
-__device__ __forceinline__ int block_excl_scan(int v, int* part /*[17]*/, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, kWave); if (lane >= off) incl += o; }
-    __syncthreads();                                   // `part` of the previous call has been read by everyone
-    if (lane == 63) part[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kLT / 64; ++i) { const int p = part[i]; if (i < wave) base += p; tot += p; }
-    total = tot;
-    return base + incl - v;
-}
 
 // BFS of a large tree: the passes over the vertices / edges (adjacency, sorting, outputs) run ACROSS THE GPU; only the level walk
 // -- a chain through the tree's depth, ~1700 levels at 200 x 304 -- is one workgroup per graph, and while the frontier is at most
@@ -305,7 +278,7 @@ constexpr int kBfsNarrow = 256;                    // widest frontier the one-wa
 constexpr int kBfsNext = 3 * kBfsNarrow + 4;
 constexpr int kBfsMaskCap = 128 * 1024;            // vertices whose 4-bit adjacency (a byte each) the walk keeps in LDS
 struct BfsWalkLds {
-    int part[17];
+    int part[kLT / 64];
     uint2 fr[2][kBfsNext];                              // the frontier of the one-wave form and the next one; <= 3 children of <= 256 nodes (the root: 4).
                                                         // General trees: (vertex, parent) pairs.  Grid trees: the same bytes as two buffers of words.
     int s_lo, s_hi, s_n, s_depth;
@@ -378,7 +351,7 @@ __device__ __forceinline__ void bfs_walk_grid(int V, int GW, int* __restrict__ l
             const uint32_t cur = e & kBfsVtx;
             const uint32_t m = i < hi ? ((uint32_t)lmask[cur] & ~(e >> 20)) : 0u;
             int total;
-            int slot = n + block_excl_scan(__popc(m), L.part, total);
+            int slot = n + block_scan_excl_i32<kLT / 64>(__popc(m), L.part, total);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if ((m >> k) & 1u) {
@@ -467,7 +440,7 @@ __device__ __forceinline__ void bfs_walk_general(int V, int* __restrict__ lv, co
                 nch += ok[k] ? 1 : 0;
             }
             int total;
-            const int pos = n + block_excl_scan(nch, L.part, total);
+            const int pos = n + block_scan_excl_i32<kLT / 64>(nch, L.part, total);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (ok[k]) {
@@ -727,7 +700,7 @@ __global__ __launch_bounds__(64) void bfsE_sort_hist_kernel(int V, int pass, cha
 // (As one flat scan of the 512 x 60 counters in bucket-major order this kernel took 30 us: every load of a thread's run of entries
 // touched 64 different lines, on one CU.)
 __global__ __launch_bounds__(kLT) void bfsE_sort_scan_kernel(int V, int nblk, char* ws_base, size_t ws_stride) {
-    __shared__ int part[17];
+    __shared__ int part[kLT / 64];
     const int b = blockIdx.x, tid = threadIdx.x;
     const BfsLargeWs w = bfs_ws(ws_base, ws_stride, b, V);
     int run = 0;
@@ -743,7 +716,7 @@ __global__ __launch_bounds__(kLT) void bfsE_sort_scan_kernel(int V, int nblk, ch
             }
         }
     int total;
-    const int base = block_excl_scan(tid < kSortBuckets ? run : 0, part, total);
+    const int base = block_scan_excl_i32<kLT / 64>(tid < kSortBuckets ? run : 0, part, total);
     if (tid < kSortBuckets) w.hist[(size_t)nblk * kSortBuckets + tid] = (uint32_t)base;
 }
 __global__ __launch_bounds__(64) void bfsE_sort_scatter_kernel(int V, int pass, char* ws_base, size_t ws_stride) {
@@ -868,22 +841,24 @@ struct RefineArgsL {
 constexpr int kPadL = 4;
 constexpr int kWinL = 8192;            // records per LDS window of the leaf->root walk (128 KB); a power of two: slot = i & (kWinL - 1)
 constexpr int kWinLv = 2048;           // levels per window at most (8 KB of level offsets)
-static size_t refine_large_block_bytes(int V) { return up16(16 * (size_t)(V + kPadL)) + up16(4 * (size_t)V) + up16(16 * (size_t)(V + kPadL)) + 16 + 3 * up16(4 * (size_t)V); }
-size_t refine_large_ws_bytes(int B, int C, int V) { return refine_large_block_bytes(V) * (size_t)(B > 0 ? B : 1) * (size_t)C; }
 
-// per (graph, channel) block of the workspace: records, parents, the second buffer of the jump rounds, one flag word
+// per (graph, channel) block of the workspace: records, parents, the second buffer of the jump rounds, one flag word (16 bytes), then for the
+// depth-free leaf->root pass the depth and the descendant-range starts
 struct RefineBlkL { float4* rec; uint32_t* parent; float4* tmp; int* bad; uint32_t* dep; uint32_t* lo0; uint32_t* lo1; };   // (no arrays: a runtime index would put the struct in scratch)
+__host__ __device__ static size_t carve_refine_blk(char* base, int V, RefineBlkL* r) {
+    Carver cv(base, 16);
+    RefineBlkL t;
+    t.rec = cv.take<float4>((size_t)(V + kPadL)); t.parent = cv.take<uint32_t>((size_t)V); t.tmp = cv.take<float4>((size_t)(V + kPadL));
+    t.bad = cv.take<int>(4);
+    t.dep = cv.take<uint32_t>((size_t)V); t.lo0 = cv.take<uint32_t>((size_t)V); t.lo1 = cv.take<uint32_t>((size_t)V);
+    if (r) *r = t;
+    return cv.bytes();
+}
+static size_t refine_large_block_bytes(int V) { return carve_refine_blk(nullptr, V, nullptr); }
+size_t refine_large_ws_bytes(int B, int C, int V) { return refine_large_block_bytes(V) * (size_t)(B > 0 ? B : 1) * (size_t)C; }
 __device__ __forceinline__ RefineBlkL refine_blk(const RefineArgsL& a, int b, int ch) {
-    char* wsb = a.ws + ((size_t)b * a.C + ch) * a.ws_stride;
     RefineBlkL r;
-    r.rec = reinterpret_cast<float4*>(wsb);
-    r.parent = reinterpret_cast<uint32_t*>(wsb + up16(16 * (size_t)(a.V + kPadL)));
-    r.tmp = reinterpret_cast<float4*>(wsb + up16(16 * (size_t)(a.V + kPadL)) + up16(4 * (size_t)a.V));
-    r.bad = reinterpret_cast<int*>(wsb + up16(16 * (size_t)(a.V + kPadL)) + up16(4 * (size_t)a.V) + up16(16 * (size_t)(a.V + kPadL)));
-    char* more = reinterpret_cast<char*>(r.bad) + 16;                 // the depth-free leaf->root pass: depth and descendant-range starts
-    r.dep = reinterpret_cast<uint32_t*>(more);
-    r.lo0 = reinterpret_cast<uint32_t*>(more + up16(4 * (size_t)a.V));
-    r.lo1 = reinterpret_cast<uint32_t*>(more + 2 * up16(4 * (size_t)a.V));
+    carve_refine_blk(a.ws + ((size_t)b * a.C + ch) * a.ws_stride, a.V, &r);
     return r;
 }
 

@@ -340,11 +340,15 @@ def test_loss_zero_instances_and_empty_image(dev):
     _check(d2, dev)
 
 
-def test_loss_from_precomputed_bits(dev):
+@pytest.mark.parametrize('batch', [
+    dict(B=2, H=96, W=160, boxes_per_img=3, seed=12, img_shapes=[(96, 131), (70, 160)], ori_shapes=[(48, 66), (210, 480)], min_box=16, max_box=80),
+    # 70 instances on 24x40 maps: stage1_kernel's work list (build_work_list) carries its total across chunks of 64 instances
+    dict(B=2, H=96, W=160, boxes_per_img=5, inst_per_box=7, seed=12, min_box=16, max_box=80),
+], ids=['n6_padded_images', 'n70_two_chunks'])
+def test_loss_from_precomputed_bits(dev, batch):
     """bxi_boxinst_loss_fwd_bwd_f32 (affinity bits given) == bxi_boxinst_eval_f32 (bits derived from Lab)."""
     from boxinstseg_amd import boxinst_mask_loss, color_affinity
-    d = synthetic.make_batch(B=2, H=96, W=160, boxes_per_img=3, seed=12, img_shapes=[(96, 131), (70, 160)],
-                             ori_shapes=[(48, 66), (210, 480)], min_box=16, max_box=80)
+    d = synthetic.make_batch(**batch)
     t = to_dev(d, dev)
     _, bits, _ = color_affinity(t['imgs'], d['img_metas'], want_similarity=False)
     outs = []
