@@ -24,6 +24,9 @@ Public surface (mirrors the reference's for this path):
     box_solov2_targets                 <-> BoxSOLOv2Head.solo_target_single over a batch (without its two F.interpolate)
     solo_cate_loss                     <-> loss_cate of both SOLOv2-style heads (focal loss on the NCHW maps, avg_factor on the device)
     parse_solo_head_cfg                : the bbox_head block of configs/discobox and configs/boxlevelset as the functions take it
+    ObjectBank, SemanticCorrSolver, superres_T <-> ObjectQueues, SemanticCorrSolver, superres_T of discobox_head.py (cross-image correspondence)
+    corr_objects                       <-> the object loop of DiscoBoxSOLOv2Head.corr_loss (retrieval, solver, loss_corr, iiu, append; no sync)
+    parse_corr_cfg                     : the loss_corr / obj_bank block of configs/discobox as the classes take it
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -38,6 +41,7 @@ from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigne
 from .box_nms import batched_nms, condinst_get_bboxes, nms, nms_with_others
 from .box_head_loss import condinst_box_loss, condinst_box_targets, parse_box_head_cfg
 from .solo_targets import SoloTargets, box_solov2_targets, parse_solo_head_cfg, solo_cate_loss, solov2_targets
+from .corr import ObjectBank, SemanticCorrSolver, corr_objects, parse_corr_cfg, superres_T
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -50,5 +54,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'box2mask_get_targets', 'MATCH_COST', 'BBOX_ASSIGNERS',
            'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes',
            'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg',
-           'solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets']
+           'solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets',
+           'ObjectBank', 'SemanticCorrSolver', 'superres_T', 'corr_objects', 'parse_corr_cfg']
 __version__ = '0.1.0'

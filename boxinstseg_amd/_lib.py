@@ -223,6 +223,28 @@ SOLO_SIGNATURES = {
                                                c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_corr.h (DiscoBox's cross-image correspondence: bank, retrieval, solver, loss_corr, iiu).  A table of its
+# own, next to FAMILIES: load() applies it and keeps the duplicate-name check across both; tests/test_host_corr.py holds it against its header.
+CORR_FEAT, CORR_MASK, CORR_MAX_OBJS, CORR_MAX_QUEUE = 7, 28, 8, 1024
+CORR_HEADERS = ('include/boxinst/boxinst_hip_corr.h',)
+CORR_SIGNATURES = {
+    'bxi_corr_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_corr_plan_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'bxi_corr_retrieve_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    'bxi_corr_solve_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                   c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_corr_loss_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_corr_grad_rescale_f32': (c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p]),
+    'bxi_corr_iiu_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                 c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_corr_append_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_int, c_void_p]),
+    'bxi_corr_superres_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    'bxi_corr_cu_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+}
+
 # every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
 # applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
 FAMILIES = [
@@ -255,7 +277,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES:
+        for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES)]:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -1,0 +1,234 @@
+"""GPU: boxinstseg_amd.corr (ObjectBank, SemanticCorrSolver, superres_T, corr_objects) against the fixture that
+tests/golden/make_golden_corr.py recorded by executing the reference's own code (tests/golden/corr.npz, corr_planes_<case>.npz).
+
+Exact: the retrieved slots and counts, the assignments, num_ins, the bank and ptr after the call, which iiu elements are zero.
+Toleranced: Cu, C, loss_sum, the gradient and iiu against the reference's fp64 values, within 4x the reference's own fp32-against-fp64
+difference (``tol_*`` of the fixture, relative to the largest fp64 magnitude of the quantity in the case).  Each case runs once per
+session; the tests share its results."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import discobox_oracle as do
+from tests import corr_ref as R
+
+pytestmark = pytest.mark.gpu
+
+G = np.load(R.GOLDEN)
+SPEC = R.load_cases()
+CFG = SPEC['cfg']
+NAMES = list(SPEC['cases'])
+MARGIN = 4.0
+_RUNS = {}
+
+
+def make_bank(dev, name):
+    from boxinstseg_amd import ObjectBank, SemanticCorrSolver
+    case, inp = SPEC['cases'][name], R.inputs_of(G, name, dev)
+    bank = ObjectBank(num_class=case['num_class'], len_queue=case['L'], fg_iou_thresh=CFG['fg_iou_thresh'], bg_iou_thresh=CFG['bg_iou_thresh'],
+                      ratio_range=CFG['ratio_range'], appear_thresh=CFG['appear_thresh'], max_retrieval_objs=CFG['max_retrieval_objs'])
+    bank.ensure(case['C'], dev)
+    bank.feature.copy_(inp['bank_feature']); bank.mask.copy_(inp['bank_mask']); bank.box.copy_(inp['bank_box']); bank.ptr.copy_(inp['bank_ptr'])
+    solver = SemanticCorrSolver(CFG['corr_exp'], CFG['corr_eps'], CFG['gaussian_filter_size'], CFG['low_score'], CFG['corr_num_iter'],
+                                CFG['corr_num_smooth_iter'], CFG['dist_kernel'])
+    return case, inp, bank, solver
+
+
+def fused(dev, name, upstream=None):
+    from boxinstseg_amd import corr_objects
+    case, inp, bank, solver = make_bank(dev, name)
+    s_feat = inp['s_feat'].clone().requires_grad_(True)
+    d = {}
+    loss, num_ins, iiu = corr_objects(s_feat, inp['s_mask'], inp['t_feat'], inp['t_mask'], inp['boxes'], inp['labels'], bank, solver, case['out_hw'],
+                                      case['min_size'], CFG['min_objs'], details=d)
+    if upstream is not None:
+        (loss * upstream).backward()
+    return dict(case=case, inp=inp, bank=bank, loss=loss.detach(), num_ins=num_ins, iiu=iiu, s_feat=s_feat, **d)
+
+
+def run(dev, name):
+    if name not in _RUNS:
+        _RUNS[name] = fused(dev, name)
+    return _RUNS[name]
+
+
+def close(got, want64, tol_key, what):
+    want = torch.from_numpy(np.asarray(want64, np.float64))
+    top = float(want.abs().max()) if want.numel() else 0.0
+    err = float((got.detach().double().cpu() - want).abs().max()) if want.numel() else 0.0
+    bound = MARGIN * float(G[f'tol_{tol_key}']) * top
+    print(f'{what}: max error {err:.3e}, bound {bound:.3e} (largest magnitude {top:.3e})')
+    assert err <= bound, f'{what}: {err:.3e} > {bound:.3e}'
+
+
+@pytest.mark.parametrize('name', NAMES)
+def test_exact_parts(dev, name):
+    r = run(dev, name)
+    count = torch.from_numpy(G[f'{name}_count'])
+    assert torch.equal(r['count'].cpu().long(), count)
+    assert torch.equal(r['ret_slot'].cpu().long(), torch.from_numpy(G[f'{name}_ret_slot']))
+    want_assign = torch.from_numpy(G[f'{name}_assign']).clone()
+    want_assign[count < CFG['min_objs']] = -1
+    assert torch.equal(r['assign'].cpu().long(), want_assign)
+    assert int(r['num_ins']) == int(G[f'{name}_num_ins'])
+    bank = r['bank']
+    for mine, key in ((bank.feature, 'after_feature'), (bank.mask, 'after_mask'), (bank.box, 'after_box')):
+        assert torch.equal(mine.cpu(), torch.from_numpy(G[f'{name}_{key}']).float()), key
+    assert torch.equal(bank.ptr.cpu(), torch.from_numpy(G[f'{name}_after_ptr']))
+    zero = np.unpackbits(G[f'{name}_iiu_zero'])[:r['iiu'].numel()].astype(bool).reshape(tuple(r['iiu'].shape))
+    assert np.array_equal(r['iiu'].cpu().numpy() == 0, zero)
+    cs = r['case']['census']
+    for i, key in ((1, 'src1'), (2, 'src2')):
+        if key in cs:
+            assert r['ret_src'][i].cpu().tolist() == cs[key]
+
+
+@pytest.mark.parametrize('name', [n for n in NAMES if len(SPEC['cases'][n]['objects'])])
+def test_toleranced_parts(dev, name):
+    r = run(dev, name)
+    planes = np.load(R.GOLDEN.replace('corr.npz', f'corr_planes_{name}.npz'))
+    close(r['Cu'], planes['Cu'], 'Cu', 'Cu')
+    close(r['C'], planes['C'], 'C', 'C')
+    close(r['loss'], G[f'{name}_loss_sum'], 'loss_sum', 'loss_sum')
+    close(r['grad'], G[f'{name}_grad'], 'grad', 'gradient')
+    close(r['iiu'], G[f'{name}_iiu'], 'iiu', 'iiu')
+
+
+def test_empty_call(dev):
+    r = run(dev, 'edges_empty')
+    assert float(r['loss']) == 0.0 and int(r['num_ins']) == 0 and tuple(r['iiu'].shape) == (0, 2, 40, 56)
+
+
+def test_two_runs_are_bit_identical(dev):
+    a, b = run(dev, 'plain'), fused(dev, 'plain')
+    for k in ('loss', 'iiu', 'Cu', 'C', 'grad', 'assign', 'ret_slot', 'count', 'scores'):
+        assert torch.equal(a[k].view(torch.int32) if a[k].dtype == torch.float32 else a[k], b[k].view(torch.int32) if b[k].dtype == torch.float32 else b[k]), k
+    assert torch.equal(a['bank'].feature, b['bank'].feature) and torch.equal(a['bank'].ptr, b['bank'].ptr)
+
+
+def test_autograd_scales_the_recorded_gradient(dev):
+    up = 0.375
+    r = fused(dev, 'in_call', upstream=torch.tensor(up, device=dev))
+    assert torch.equal(r['s_feat'].grad, r['grad'] * up)
+    close(r['s_feat'].grad, G['in_call_grad'] * up, 'grad', 'scaled gradient')
+
+
+class _Query:
+    def __init__(self, mask, feature, box, category):
+        self.mask, self.feature, self.box, self.category = mask, feature, box, category
+
+
+@pytest.mark.parametrize('name', ['in_call', 'one_fails_each'])
+def test_drop_ins_one_object_at_a_time(dev, name):
+    """The reference's loop written with get_similar_obj / solve / superres_T / append gives what the fused call gives."""
+    from boxinstseg_amd import superres_T
+    r = run(dev, name)
+    case, inp, bank, solver = make_bank(dev, name)
+    H, W = case['out_hw']
+    N = inp['labels'].shape[0]
+    s_feat = inp['s_feat'].clone().requires_grad_(True)
+    loss, iiu = torch.zeros((), device=dev), torch.zeros(N, 2, H, W, device=dev)
+    for i in range(N):
+        q = _Query(inp['s_mask'][i:i + 1], inp['s_feat'][i:i + 1], inp['boxes'][i:i + 1], int(inp['labels'][i]))
+        kobjs = bank.get_similar_obj(q)
+        n = kobjs['mask'].shape[0]
+        assert n == int(r['count'][i])
+        if n >= CFG['min_objs']:
+            Cu, T, fg_mask, bg_mask = solver.solve(q, kobjs, s_feat[i:i + 1])
+            assert torch.equal(Cu.detach(), r['Cu'][i, :n]) and torch.equal(T, r['C'][i, :n])
+            p = torch.softmax(Cu, 2).reshape(-1, 49)
+            loss = loss + torch.nn.functional.cross_entropy(p, T.argmax(2).reshape(-1))
+            with torch.no_grad():
+                T = T * p.reshape(T.shape)
+                T = T / (T.sum(2, keepdim=True) + 1e-5)
+                Ts = superres_T(T, (7, 7), (28, 28))
+                v = kobjs['mask'].reshape(n, -1, 1)
+                fg = torch.matmul(Ts * (fg_mask > 0.5).float(), v.clamp(0.1, 0.9)).mean(0).reshape(1, 1, 28, 28)
+                bg = torch.matmul(Ts * (bg_mask > 0.5).float(), (1 - v).clamp(0.1, 0.9)).mean(0).reshape(1, 1, 28, 28)
+                x1, y1, x2, y2 = (int(v) for v in inp['boxes'][i])
+                for ch, ci in ((0, bg), (1, fg)):
+                    iiu[i, ch, y1:y2, x1:x2] = torch.nn.functional.interpolate(ci, (y2 - y1, x2 - x1), mode='bilinear', align_corners=False)[0, 0]
+        b = inp['boxes'][i]
+        if (b[2] - b[0]) > case['min_size'] and (b[3] - b[1]) > case['min_size']:
+            bank.append(int(inp['labels'][i]), i, inp['t_feat'], inp['t_mask'], inp['boxes'])
+    for a, b in ((bank.feature, r['bank'].feature), (bank.mask, r['bank'].mask), (bank.box, r['bank'].box), (bank.ptr, r['bank'].ptr)):
+        assert torch.equal(a, b)
+    close(loss, G[f'{name}_loss_sum'], 'loss_sum', 'drop-in loss_sum')
+    close(iiu, G[f'{name}_iiu'], 'iiu', 'drop-in iiu')
+    loss.backward()
+    close(s_feat.grad, G[f'{name}_grad'], 'grad', 'drop-in gradient')
+
+
+def test_meanfield_takes_the_produced_iiu(dev):
+    """MeanField.forward fed the iiu of the fused call against the numpy restatement of the mean field fed the recorded one."""
+    from boxinstseg_amd import MeanField
+    r = run(dev, 'plain')
+    H, W = r['case']['out_hw']
+    N = r['iiu'].shape[0]
+    rng = np.random.default_rng(77)
+    yy, xx = np.mgrid[0:H, 0:W]
+    feat = (np.stack([np.sin(xx / 5.0), np.cos(yy / 6.0 + xx / 9.0), 0.3 * np.sin(yy / 3.0)]) + 0.1 * rng.standard_normal((3, H, W))).astype(np.float32)
+    x = rng.uniform(0, 1, size=(N, H, W)).astype(np.float32)
+    t = np.zeros((N, H, W), np.uint8)
+    for i, b in enumerate(r['inp']['boxes'].cpu().numpy().astype(int)):
+        t[i, b[1]:b[3], b[0]:b[2]] = 1
+    mf = MeanField(torch.from_numpy(feat[None]).to(dev), alpha0=2.0, theta0=0.5, theta1=30.0, iter=10, kernel_size=3, base=0.1)
+    ret, valid = mf(torch.from_numpy(x).to(dev).unsqueeze(1), torch.from_numpy(t).to(dev).unsqueeze(1), r['iiu'])
+    Ko = do.meanfield_kernel(feat, 3, 2.0, 0.5, 30.0)
+    want, wv = do.meanfield_forward(Ko, x, t, 10, 0.1, G['plain_iiu'].astype(np.float32), 0.01)
+    bad = int((ret.squeeze(1).cpu().numpy() != want).sum())
+    assert bad <= max(1, int(2e-4 * want.size)), f'{bad} of {want.size} labels differ'      # the bound of test_gpu_discobox.py:test_meanfield_fuzz
+    if bad == 0:
+        assert np.array_equal(valid.cpu().numpy(), wv)
+
+
+def test_odd_sizes_and_other_settings_against_the_restatement(dev):
+    """What the fixture's cases do not reach: a channel count that is no multiple of the 16-channel stage or of the five channel groups,
+    three retrieved objects at most and two needed (an object with count between the two runs with fewer work items), dist_kernel 5, three
+    rounds of two smoothing steps, a queue of five, an odd canvas.  The referee is the restatement in fp64 on the same inputs; every entry
+    is a 'good' one, so every score is far from its threshold."""
+    from boxinstseg_amd import ObjectBank, SemanticCorrSolver, corr_objects
+    C, L, K, N, hw = 21, 5, 3, 3, (33, 47)
+    cfg = dict(CFG, max_retrieval_objs=K, min_objs=2, dist_kernel=5, corr_num_iter=3, corr_num_smooth_iter=2, min_size=6)
+    rng = np.random.RandomState(5)
+    base = np.abs(rng.standard_normal((C, 7, 7)))
+    entry = lambda: (R.half(R.feature(base, rng)), R.half(R.snap(R.blob(13.5 + rng.uniform(-0.4, 0.4), 13.5, 9.0 + rng.uniform(-0.3, 0.3)))))  # noqa: E731
+    inp = dict(bank_feature=np.zeros((1, L, C, 7, 7), np.float32), bank_mask=np.zeros((1, L, 28, 28), np.float32), bank_box=np.zeros((1, L, 4), np.float32),
+               bank_ptr=np.array([4], np.int32), s_feat=np.zeros((N, C, 7, 7), np.float32), s_mask=np.zeros((N, 28, 28), np.float32),
+               t_feat=np.zeros((N, C, 7, 7), np.float32), t_mask=np.zeros((N, 28, 28), np.float32),
+               boxes=np.array([[3, 2, 24, 21], [20, 9, 47, 33], [0, 5, 17, 20]], np.float32), labels=np.zeros(N, np.int64))
+    for s in (1, 3):
+        inp['bank_feature'][0, s], inp['bank_mask'][0, s] = entry()
+        inp['bank_box'][0, s] = [0, 0, 20, 19]
+    for i in range(N):
+        inp['s_feat'][i], inp['s_mask'][i] = entry()
+        inp['t_feat'][i], inp['t_mask'][i] = entry()
+    ref_in = {k: torch.from_numpy(v.copy()) for k, v in inp.items()}
+    ref_in = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in ref_in.items()}
+    ref_in['s_feat'].requires_grad_(True)
+    want = R.corr_objects(ref_in, cfg, hw, record=True)
+    assert want['count'].tolist() == [2, 3, 3] and want['num_ins'] == 3          # two stored, then the call's own appends at slots 4 and 0
+    want_grad = torch.autograd.grad(want['loss_sum'], ref_in['s_feat'])[0]
+    top = torch.cat([want['C'][i, :int(n)] for i, n in enumerate(want['count'])]).topk(2, dim=2).values
+    assert float(((top[..., 0] - top[..., 1]) / top[..., 0]).min()) >= 1e-3      # no arg-max of C is a near tie
+    t = {k: torch.from_numpy(v).to(dev) for k, v in inp.items()}
+    bank = ObjectBank(1, L, cfg['fg_iou_thresh'], cfg['bg_iou_thresh'], cfg['ratio_range'], cfg['appear_thresh'], K)
+    bank.ensure(C, dev)
+    bank.feature.copy_(t['bank_feature']); bank.mask.copy_(t['bank_mask']); bank.box.copy_(t['bank_box']); bank.ptr.copy_(t['bank_ptr'])
+    solver = SemanticCorrSolver(1.0, 0.05, 3, 0.3, cfg['corr_num_iter'], cfg['corr_num_smooth_iter'], cfg['dist_kernel'])
+    s_feat = t['s_feat'].clone().requires_grad_(True)
+    d = {}
+    loss, num_ins, iiu = corr_objects(s_feat, t['s_mask'], t['t_feat'], t['t_mask'], t['boxes'], t['labels'], bank, solver, hw, cfg['min_size'], cfg['min_objs'],
+                                      details=d)
+    loss.backward()
+    assert torch.equal(d['count'].cpu().long(), want['count']) and torch.equal(d['ret_slot'].cpu().long(), want['ret_slot'])
+    assert torch.equal(d['assign'].cpu().long(), want['assign']) and int(num_ins) == 3
+    assert d['ret_src'].cpu().tolist() == [[-1, -1, -1], [-1, -1, 0], [1, -1, -1]] and bank.ptr.cpu().tolist() == [2]
+    for mine, ref in ((bank.feature, ref_in['bank_feature']), (bank.mask, ref_in['bank_mask']), (bank.box, ref_in['bank_box'])):
+        assert torch.equal(mine.cpu(), ref.float())
+    assert torch.equal(iiu.cpu() == 0, want['iiu'] == 0)
+    close(d['Cu'], want['Cu'], 'Cu', 'Cu')
+    close(d['C'], want['C'], 'C', 'C')
+    close(loss, want['loss_sum'].detach(), 'loss_sum', 'loss_sum')
+    close(s_feat.grad, want_grad, 'grad', 'gradient')
+    close(iiu, want['iiu'], 'iiu', 'iiu')
