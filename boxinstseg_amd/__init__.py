@@ -27,6 +27,9 @@ Public surface (mirrors the reference's for this path):
     ObjectBank, SemanticCorrSolver, superres_T <-> ObjectQueues, SemanticCorrSolver, superres_T of discobox_head.py (cross-image correspondence)
     corr_objects                       <-> the object loop of DiscoBoxSOLOv2Head.corr_loss (retrieval, solver, loss_corr, iiu, append; no sync)
     parse_corr_cfg                     : the loss_corr / obj_bank block of configs/discobox as the classes take it
+    roi_align, RoIAlign                <-> mmcv.ops.roi_align / RoIAlign (pool_mode='avg'; restated arithmetic, forward and backward)
+    relu_and_l2_norm_feat, roi_feat_norm, sigmoid_roi_masks, target_boxes : the pieces of the front of corr_loss (discobox_head.py:1018-1057)
+    corr_level                         <-> one level of DiscoBoxSOLOv2Head.corr_loss (:1018-1127): the front, then corr_objects; no sync
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -42,6 +45,7 @@ from .box_nms import batched_nms, condinst_get_bboxes, nms, nms_with_others
 from .box_head_loss import condinst_box_loss, condinst_box_targets, parse_box_head_cfg
 from .solo_targets import SoloTargets, box_solov2_targets, parse_solo_head_cfg, solo_cate_loss, solov2_targets
 from .corr import ObjectBank, SemanticCorrSolver, corr_objects, parse_corr_cfg, superres_T
+from .roi_align import RoIAlign, corr_level, relu_and_l2_norm_feat, roi_align, roi_feat_norm, sigmoid_roi_masks, target_boxes
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -55,5 +59,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes',
            'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg',
            'solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets',
-           'ObjectBank', 'SemanticCorrSolver', 'superres_T', 'corr_objects', 'parse_corr_cfg']
+           'ObjectBank', 'SemanticCorrSolver', 'superres_T', 'corr_objects', 'parse_corr_cfg',
+           'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level']
 __version__ = '0.1.0'

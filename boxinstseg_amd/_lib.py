@@ -245,6 +245,23 @@ CORR_SIGNATURES = {
     'bxi_corr_cu_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_roi.h (RoIAlign forward / backward and the front of one level of DiscoBox's corr_loss).  A table of its own like
+# CORR_SIGNATURES: load() applies it and keeps the duplicate-name check across all of them; tests/test_host_roi.py holds it against its header.
+ROI_MAX_POOL, ROI_MAX_SAMPLING, ROI_MAX_SIDE, ROI_FUSED_MAX_C, ROI_FEAT, ROI_SIGMOID = 64, 64, 16384, 8192, 7, 1
+ROI_HEADERS = ('include/boxinst/boxinst_hip_roi.h',)
+ROI_SIGNATURES = {
+    'bxi_roi_target_boxes_u8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bxi_roi_align_forward_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_void_p,
+                                          c_void_p]),
+    'bxi_roi_align_backward_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p,
+                                           c_void_p]),
+    'bxi_roi_feat_norm_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'bxi_roi_feat_norm_forward_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p, c_void_p,
+                                              c_size_t, c_void_p]),
+    'bxi_roi_feat_norm_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_void_p,
+                                               c_void_p, c_size_t, c_void_p]),
+}
+
 # every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
 # applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
 FAMILIES = [
@@ -277,7 +294,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES)]:
+        for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES)]:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')
