@@ -30,6 +30,9 @@ Public surface (mirrors the reference's for this path):
     roi_align, RoIAlign                <-> mmcv.ops.roi_align / RoIAlign (pool_mode='avg'; restated arithmetic, forward and backward)
     relu_and_l2_norm_feat, roi_feat_norm, sigmoid_roi_masks, target_boxes : the pieces of the front of corr_loss (discobox_head.py:1018-1057)
     corr_level                         <-> one level of DiscoBoxSOLOv2Head.corr_loss (:1018-1127): the front, then corr_objects; no sync
+    multi_scale_deformable_attn        <-> mmcv.ops.multi_scale_deform_attn.MultiScaleDeformableAttnFunction.apply (restated arithmetic)
+    multi_scale_deformable_attn_fused  : the same from reference points, raw offsets and raw logits (normaliser and softmax in the kernel)
+    MultiScaleDeformableAttention      <-> mmcv's module, the self-attention of Box2Mask's MSDeformAttnPixelDecoder; ATTENTION, build_attention
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -37,7 +40,7 @@ from .dynamic import DynamicMaskHead, dynamic_mask_forward, paste_masks, paste_m
 from .mask_head import CondInstMaskHead
 from .discobox import MeanField, dice_loss, meanfield_forward, meanfield_kernel, mil_loss
 from .levelset import LCM, BoxProjectionLoss, LevelsetLoss, LocalConsistencyModule, region_levelset
-from .registry import BBOX_ASSIGNERS, HEADS, LOSSES, MATCH_COST, build_assigner, build_head, build_loss, build_match_cost
+from .registry import ATTENTION, BBOX_ASSIGNERS, HEADS, LOSSES, MATCH_COST, build_assigner, build_attention, build_head, build_loss, build_match_cost
 from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
 from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask_matrix_nms, seg_nms
 from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigner, box2mask_get_targets
@@ -46,6 +49,7 @@ from .box_head_loss import condinst_box_loss, condinst_box_targets, parse_box_he
 from .solo_targets import SoloTargets, box_solov2_targets, parse_solo_head_cfg, solo_cate_loss, solov2_targets
 from .corr import ObjectBank, SemanticCorrSolver, corr_objects, parse_corr_cfg, superres_T
 from .roi_align import RoIAlign, corr_level, relu_and_l2_norm_feat, roi_align, roi_feat_norm, sigmoid_roi_masks, target_boxes
+from .msda import MultiScaleDeformableAttention, multi_scale_deformable_attn, multi_scale_deformable_attn_fused
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -60,5 +64,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg',
            'solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets',
            'ObjectBank', 'SemanticCorrSolver', 'superres_T', 'corr_objects', 'parse_corr_cfg',
-           'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level']
+           'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level',
+           'multi_scale_deformable_attn', 'multi_scale_deformable_attn_fused', 'MultiScaleDeformableAttention', 'ATTENTION', 'build_attention']
 __version__ = '0.1.0'

@@ -262,6 +262,18 @@ ROI_SIGNATURES = {
                                                c_void_p, c_size_t, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_msda.h (multi-scale deformable attention, forward and backward).  A table of its own like CORR_SIGNATURES and
+# ROI_SIGNATURES: load() applies it under the same duplicate-name check; tests/test_host_msda.py holds it against its header.
+MSDA_MAX_LEVELS, MSDA_MAX_POINTS, MSDA_MIN_HEAD_DIM, MSDA_MAX_HEAD_DIM, MSDA_FUSED, MSDA_MAX_CELL_SAMPLES = 8, 8, 8, 64, 1, 1 << 22
+MSDA_HEADERS = ('include/boxinst/boxinst_hip_msda.h',)
+MSDA_SIGNATURES = {
+    'bxi_msda_forward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     c_void_p, c_void_p]),
+    'bxi_msda_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'bxi_msda_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
 # applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
 FAMILIES = [
@@ -294,7 +306,8 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES)]:
+        for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES),
+                                                   ('msda', MSDA_HEADERS, MSDA_SIGNATURES)]:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

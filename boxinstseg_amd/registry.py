@@ -108,6 +108,17 @@ def _make_assigners():
 BBOX_ASSIGNERS = _make_assigners()    # MaskHungarianAssigner (mmdet/core/bbox/builder.py: BBOX_ASSIGNERS)
 
 
+def _make_attention():
+    try:
+        from mmcv.cnn.bricks.registry import ATTENTION as mm_attention
+        return _MMDetHeads(mm_attention)
+    except Exception:
+        return Registry('attention')
+
+
+ATTENTION = _make_attention()         # MultiScaleDeformableAttention (mmcv/cnn/bricks/registry.py: ATTENTION)
+
+
 def build_head(cfg: dict, default_args: Optional[dict] = None):
     """``mmdet.models.builder.build_head`` for the heads this package provides."""
     return HEADS.build(cfg, default_args=default_args)
@@ -126,3 +137,8 @@ def build_match_cost(cfg: dict, default_args: Optional[dict] = None):
 def build_assigner(cfg: dict, default_args: Optional[dict] = None):
     """``mmdet.core.bbox.build_assigner`` for the assigners this package provides."""
     return BBOX_ASSIGNERS.build(cfg, default_args=default_args)
+
+
+def build_attention(cfg: dict, default_args: Optional[dict] = None):
+    """``mmcv.cnn.bricks.transformer.build_attention`` for the attention modules this package provides."""
+    return ATTENTION.build(cfg, default_args=default_args)
