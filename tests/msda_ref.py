@@ -9,6 +9,9 @@ mmcv's op never ran next to this library: its arithmetic is restated from its do
                        one step of the loop, taken for all (b, q, m) at once.
     fused_to_plain     reference points, raw offsets, raw logits -> locations (ref + off / (W, H)) and softmax weights
     RefMSDA            the module restated: the same four linear layers, offset normaliser, softmax, box form, residual
+    dyadic_case        inputs that are small dyadic rationals: every intermediate of the forward and of the gradients is exact in fp32, so
+                       msda_scalar gives the same bits in fp32 and in fp64 and the kernel has to give them too (no fixture file: seeded)
+    cell_hits          how many corners of valid samples land on every cell of value: the count of the fixed-point quantisation bound
 
 The fixture (tests/golden/msda.npz, msda_decoder.npz, msda_decoder_inputs.npz, msda_cases.json; make_golden_msda.py) holds the inputs of every case, the fp64
 results of msda_scalar and the tolerances: 4 x the fp32-against-fp64 difference of msda_scalar itself."""
@@ -236,3 +239,88 @@ def off_grid(t, spec, skip=None):
     if skip is not None:
         bad = bad & ~skip
     return not bool(bad.any())
+
+
+# ---- exact cases ----------------------------------------------------------------------------------------------------------------
+def dyadic_case(seed, B, Q, M, D, shapes, P, fused, gmax=8, scale_b1=0):
+    """Inputs on which fp32 arithmetic is exact (every level side a power of two), as fp32 CPU tensors, and the spec run_case takes.
+
+    value and grad_out are integers in [-8, 8] and [-gmax, gmax], one grad_out of batch 0 planted at gmax: max|grad_out| = gmax.
+    plain: locations are multiples of 1/32 in [-6/32, 38/32] (inside, outside, on pixel centres, on h = -1), weights multiples of 1/16 in
+           [-1, 1] with one planted 1: Mx = gmax, a power of two for gmax = 8 and not for gmax = 7.
+    fused: reference points multiples of 1/8 in [0, 1], offsets multiples of 1/8 in [-2, 2], logits 0 at exactly four of the L * P
+           positions of every (b, q, m) and -inf elsewhere: the softmax is 1/4 four times and 0 elsewhere, exactly.
+    scale_b1 = k multiplies grad_out[1] by 2^-k (exact): a batch item whose gradients are small against Mx."""
+    assert all(h & (h - 1) == 0 and w & (w - 1) == 0 for h, w in shapes)
+    assert not fused or len(shapes) * P >= 4
+    gen = torch.Generator().manual_seed(seed)
+    L, S = len(shapes), sum(h * w for h, w in shapes)
+
+    def ints(lo, hi, *size):
+        return torch.randint(lo, hi + 1, size, generator=gen).float()
+
+    t = {'value': ints(-8, 8, B, S, M, D), 'grad_out': ints(-gmax, gmax, B, Q, M * D)}
+    t['grad_out'][0, 0, 0] = gmax
+    if fused:
+        t['ref'] = ints(0, 8, B, Q, L, 2) / 8
+        t['off'] = ints(-16, 16, B, Q, M, L, P, 2) / 8
+        logits = torch.full((B * Q * M, L * P), float('-inf'))
+        for row in logits:
+            row[torch.randperm(L * P, generator=gen)[:4]] = 0.0
+        t['logits'] = logits.view(B, Q, M, L * P)
+    else:
+        t['loc'] = ints(-6, 38, B, Q, M, L, P, 2) / 32
+        t['w'] = ints(-16, 16, B, Q, M, L, P) / 16
+        t['w'][0, 0, 0, 0, 0] = 1.0
+    if scale_b1:
+        t['grad_out'][1] = torch.ldexp(t['grad_out'][1], torch.tensor(-scale_b1))
+    return t, dict(B=B, Q=Q, M=M, D=D, P=P, shapes=[list(s) for s in shapes], fused=fused)
+
+
+def fixed_point_mx(t, spec):
+    """Mx of include/boxinst/boxinst_hip_msda.h in fp64: max|grad_out| * max|weight|, the weight maximum 1 in the fused form."""
+    mx = float(t['grad_out'].double().abs().max())
+    return mx if spec['fused'] else mx * float(t['w'].double().abs().max())
+
+
+def cell_hits(shapes, loc, B, S, M):
+    """n [B,S,M] int64: over all samples of loc [B,Q,M,L,P,2] that count (h > -1, w > -1, h < H, w < W, strict; a NaN fails), the corners
+    that land inside the map, per cell.  An upper bound on the contributions a cell of grad_value receives: a corner of weight 0 adds
+    nothing to the sum and no error."""
+    n = torch.zeros(B, S, M, dtype=torch.int64)
+    bi = torch.arange(B).view(B, 1, 1, 1).expand(loc.shape[:3] + loc.shape[4:5])
+    mi = torch.arange(M).view(1, 1, M, 1).expand_as(bi)
+    for lvl, ((H, W), start) in enumerate(zip(shapes, level_starts(shapes))):
+        h, w = loc[:, :, :, lvl, :, 1] * H - 0.5, loc[:, :, :, lvl, :, 0] * W - 0.5
+        valid = (h > -1) & (w > -1) & (h < H) & (w < W)
+        h0 = torch.where(valid, h, torch.zeros_like(h)).floor().long()
+        w0 = torch.where(valid, w, torch.zeros_like(w)).floor().long()
+        for dy in (0, 1):
+            for dx in (0, 1):
+                y, x = h0 + dy, w0 + dx
+                inside = valid & (y >= 0) & (y <= H - 1) & (x >= 0) & (x <= W - 1)
+                cell = start + y.clamp(0, H - 1) * W + x.clamp(0, W - 1)
+                n.index_put_((bi[inside], cell[inside], mi[inside]), torch.ones((), dtype=torch.int64), accumulate=True)
+    return n
+
+
+# the dyadic cases of tests/test_gpu_msda_fixed_point.py: name -> the arguments of dyadic_case without gmax / scale_b1
+DYADIC = {
+    'plain_d8_tail': dict(seed=1, B=2, Q=7, M=3, D=8, shapes=[(4, 8), (2, 2)], P=8, fused=False),      # L * P = 16 > D; 42 items: a tail group
+    'plain_d64': dict(seed=3, B=1, Q=9, M=1, D=64, shapes=[(2, 4)], P=2, fused=False),
+    'fused_d16': dict(seed=2, B=2, Q=5, M=3, D=16, shapes=[(4, 4), (8, 2)], P=4, fused=True),
+    'fused_d32': dict(seed=4, B=2, Q=3, M=5, D=32, shapes=[(8, 8), (4, 4), (2, 2), (1, 1)], P=2, fused=True),
+}
+# (case, gmax, scale_b1): Mx a power of two, every result exact; Mx = 7 and a batch item 2^-32 below the rest, the quantisation bound
+DYADIC_EXACT = [(n, 8, 0) for n in DYADIC]
+DYADIC_BOUND = [(n, 7, 0) for n in DYADIC] + [('plain_d8_tail', 7, 32), ('plain_d8_tail', 8, 32)]
+
+
+def dyadic(name, gmax=8, scale_b1=0):
+    return dyadic_case(gmax=gmax, scale_b1=scale_b1, **DYADIC[name])
+
+
+def plain_locations(t, spec):
+    """The fp64 locations [B,Q,M,L,P,2] of a case of either form."""
+    shapes = [tuple(s) for s in spec['shapes']]
+    return fused_to_plain(shapes, t['ref'].double(), t['off'].double(), t['logits'].double())[0] if spec['fused'] else t['loc'].double()

@@ -6,7 +6,9 @@
 * include/boxinst/boxinst_hip_msda.h, the library's exports and _lib.MSDA_SIGNATURES name the same entry points, none of them in another table,
   and each is run by a named guarded test or is a ``_bytes`` query;
 * the attn_cfgs block of the reference's Box2Mask configs builds the module; its state-dict keys and init_weights are the restated module's;
-* bad arguments, CPU tensors, half precision and shapes outside the support set fail before any launch."""
+* bad arguments, CPU tensors, half precision and shapes outside the support set fail before any launch;
+* the premise of tests/test_gpu_msda_fixed_point.py holds for the restatement alone: on the dyadic cases fp32 and fp64 give the same bits;
+  cell_hits counts a case counted by hand."""
 import importlib
 import importlib.util
 import inspect
@@ -317,3 +319,50 @@ def test_abi_validation_without_device():
     assert bwd(D=12) == U and bwd(flags=4) == -3 and bwd(Q=-1) == -2
     assert bwd(ws=None) == -5 and bwd(bytes=need - 1) == -5 and bwd(ws=X + 8) == -5
     assert bwd(gv=None) == -1 and bwd(g=None) == -1 and bwd(ga=None) == -1 and bwd(flags=1, off=None) == -1
+
+
+@pytest.mark.parametrize('name,gmax,scale_b1', sorted(set(R.DYADIC_EXACT + R.DYADIC_BOUND)))
+def test_dyadic_cases_are_exact_in_fp32(name, gmax, scale_b1):
+    """The premise of the GPU file, for the restatement alone: every intermediate is exact in fp32, so the fp32 run IS the fp64 run."""
+    t, spec = R.dyadic(name, gmax, scale_b1)
+    arg = R.DYADIC[name]
+    assert (spec['B'], spec['Q'], spec['M'], spec['D'], spec['P']) == (arg['B'], arg['Q'], arg['M'], arg['D'], arg['P'])
+    assert all(v.dtype == torch.float32 for v in t.values()) and float(t['grad_out'].abs().max()) == gmax == float(t['grad_out'][0].abs().max())
+    assert R.fixed_point_mx(t, spec) == gmax
+    if scale_b1:
+        assert 0 < float(t['grad_out'][1].abs().max()) <= gmax * 2.0 ** -scale_b1
+    if spec['fused']:
+        assert bool(((t['logits'] == 0).sum(-1) == 4).all()) and bool(((t['logits'] == 0) | (t['logits'] == float('-inf'))).all())
+    else:
+        assert float(t['w'].abs().max()) == 1.0
+    r32, r64 = R.run_case(t, spec), R.run_case({k: v.double() for k, v in t.items()}, spec)
+    assert sorted(r32) == sorted(r64) and len(r64) == 4
+    for k in r64:
+        assert r32[k].dtype == torch.float32 and r64[k].dtype == torch.float64
+        assert bool(torch.isfinite(r64[k]).all()) and float(r64[k].abs().max()) > 0, k
+        assert torch.equal(r64[k].float().double(), r64[k]), f'{k}: not representable in fp32'
+        assert torch.equal(r32[k].view(torch.int32), r64[k].float().view(torch.int32)), k
+    # some sample of every case is outside, some cell is hit more than once, and an Mx of 8 really is a power of two
+    n = R.cell_hits([tuple(s) for s in spec['shapes']], R.plain_locations(t, spec), spec['B'], t['value'].shape[1], spec['M'])
+    assert int(n.max()) > 1 and int(n.sum()) < 4 * spec['B'] * spec['Q'] * spec['M'] * len(spec['shapes']) * spec['P']
+
+
+def test_cell_hits_by_hand():
+    """Two levels, 2 x 2 and 1 x 1, one (b, q, m), six samples each.
+    level 0: (.5, .5) h = w = .5, four corners inside -> cells 0 1 2 3;  (.25, .25) h = w = 0 on a pixel centre: the four corners still land
+             inside (three of weight 0: an upper bound) -> 0 1 2 3;  (0, 0) h = w = -.5: only (0, 0) -> cell 0;  (-.25, .5) w = -1: does not
+             count;  NaN: does not count;  (1, .25) w = 1.5, h = 0: (0, 1) and (1, 1) -> cells 1 3.          totals 3 3 2 3
+    level 1: (.5, .5) h = w = 0: only (0, 0) -> cell 4;  (1, 1) h = w = .5: only (0, 0) -> cell 4;  (1.5, .5) w = 1 = W: does not count;
+             (-.5, .5) w = -1: does not count;  (5, 5), (inf, .5): do not count.                                total 2"""
+    nan, inf = float('nan'), float('inf')
+    loc = torch.tensor([[(.5, .5), (.25, .25), (0., 0.), (-.25, .5), (nan, .5), (1., .25)],
+                        [(.5, .5), (1., 1.), (1.5, .5), (-.5, .5), (5., 5.), (inf, .5)]], dtype=torch.float64).view(1, 1, 1, 2, 6, 2)
+    n = R.cell_hits([(2, 2), (1, 1)], loc, 1, 5, 1)
+    assert n.dtype == torch.int64 and tuple(n.shape) == (1, 5, 1) and n.view(-1).tolist() == [3, 3, 2, 3, 2]
+    # B and M index the count: the same samples in batch 1, head 2 of a [2, 5, 3] count land there and nowhere else
+    big = torch.full((2, 1, 3, 2, 6, 2), 9.0, dtype=torch.float64)
+    big[1, 0, 2] = loc[0, 0, 0]
+    n = R.cell_hits([(2, 2), (1, 1)], big, 2, 5, 3)
+    assert n[1, :, 2].tolist() == [3, 3, 2, 3, 2] and int(n.sum()) == 13
+    # fp32 locations count the same
+    assert torch.equal(R.cell_hits([(2, 2), (1, 1)], loc.float(), 1, 5, 1), R.cell_hits([(2, 2), (1, 1)], loc, 1, 5, 1))
