@@ -12,6 +12,8 @@ Public surface (mirrors the reference's for this path):
     MinimumSpanningTree, TreeFilter2D, mst, bfs, refine <-> mmdet.ops.tree_filter
     mask_matrix_nms                    <-> mmdet.core.post_processing.mask_matrix_nms
     seg_nms, box_solov2_get_seg_single, discobox_get_seg_single : the test-time block of the SOLOv2-style heads (get_seg_single)
+    seg_paste                          : the two resizes and the threshold that end get_seg_single as one kernel, with area and box per mask
+    solo_get_seg, solo_format_results  <-> get_seg of both SOLOv2-style heads / format_results of their detectors (one host copy, one sync)
     ClassificationCost, BoxMatchingCost, MaskHungarianAssigner <-> mmdet.core.bbox match costs / assigner of Box2Mask
     box2mask_get_targets               <-> Box2MaskHead.get_targets (matching cost and Hungarian assignment of a whole batch)
     nms, batched_nms                   <-> mmcv.ops.nms.nms / batched_nms (greedy box NMS, one workgroup per image)
@@ -43,6 +45,7 @@ from .levelset import LCM, BoxProjectionLoss, LevelsetLoss, LocalConsistencyModu
 from .registry import ATTENTION, BBOX_ASSIGNERS, HEADS, LOSSES, MATCH_COST, build_assigner, build_attention, build_head, build_loss, build_match_cost
 from .tree_filter import MinimumSpanningTree, TreeFilter2D, bfs, mst, refine
 from .matrix_nms import box_solov2_get_seg_single, discobox_get_seg_single, mask_matrix_nms, seg_nms
+from .seg_paste import seg_paste, solo_format_results, solo_get_seg
 from .box_match import BoxMatchingCost, ClassificationCost, MaskHungarianAssigner, box2mask_get_targets
 from .box_nms import batched_nms, condinst_get_bboxes, nms, nms_with_others
 from .box_head_loss import condinst_box_loss, condinst_box_targets, parse_box_head_cfg
@@ -59,6 +62,7 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'BoxProjectionLoss', 'LevelsetLoss', 'region_levelset', 'LocalConsistencyModule', 'LCM', 'LOSSES', 'build_loss',
            'MinimumSpanningTree', 'TreeFilter2D', 'mst', 'bfs', 'refine',
            'mask_matrix_nms', 'seg_nms', 'box_solov2_get_seg_single', 'discobox_get_seg_single',
+           'seg_paste', 'solo_get_seg', 'solo_format_results',
            'ClassificationCost', 'BoxMatchingCost', 'MaskHungarianAssigner', 'box2mask_get_targets', 'MATCH_COST', 'BBOX_ASSIGNERS',
            'build_match_cost', 'build_assigner', 'nms', 'batched_nms', 'nms_with_others', 'condinst_get_bboxes',
            'condinst_box_targets', 'condinst_box_loss', 'parse_box_head_cfg',

@@ -274,6 +274,16 @@ MSDA_SIGNATURES = {
                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_seg.h (the final masks of the SOLOv2-style heads: resize, crop, threshold, area and box of the kept candidates).
+# A table of its own like the three above: load() applies it under the same duplicate-name check; tests/test_host_seg_paste.py holds it
+# against its header.
+SEG_HEADERS = ('include/boxinst/boxinst_hip_seg.h',)
+SEG_SIGNATURES = {
+    'bxi_seg_paste_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_seg_paste_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
 # applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
 FAMILIES = [
@@ -307,7 +317,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
         owner = {}
         for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES),
-                                                   ('msda', MSDA_HEADERS, MSDA_SIGNATURES)]:
+                                                   ('msda', MSDA_HEADERS, MSDA_SIGNATURES), ('seg', SEG_HEADERS, SEG_SIGNATURES)]:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -7,7 +7,8 @@ area, mask scoring and Matrix NMS on bit-packed masks (csrc/matrix_nms.hip, incl
     discobox_get_seg_single    <-> DiscoBoxSOLOv2Head.get_seg_single (discobox_head.py:1560-1660)
 
 There is no CPU or PyTorch fallback: CPU tensors raise.  What stays in torch is what has data-dependent sizes in the reference
-too (``nonzero``, the sorts, ``filter_thr`` / ``max_num``) and the resizes of the few kept masks.
+too (``nonzero``, the sorts, ``filter_thr`` / ``max_num``).  The resizes and the final threshold of the kept masks are one more kernel
+(seg_paste.py, csrc/seg_paste.hip).
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._common import cfg_require, current_stream, need_cuda
+from .seg_paste import paste_results
 
 __all__ = ['mask_matrix_nms', 'seg_nms', 'pack_probs', 'pack_masks', 'matrix_nms_decay', 'matrix_nms_scores',
            'box_solov2_get_seg_single', 'discobox_get_seg_single']
@@ -192,32 +194,32 @@ def _level_strides(cate_scores, cate_labels, seg_num_grids, strides):
 
 def _results(img_meta, scores, labels, masks):
     meta = dict(img_meta)
-    return types.SimpleNamespace(scores=scores, labels=labels, masks=masks, img_shape=meta['img_shape'], ori_shape=meta['ori_shape'])
+    return types.SimpleNamespace(scores=scores, labels=labels, masks=masks, img_shape=meta['img_shape'], ori_shape=meta['ori_shape'],
+                                 mask_stats=None)
 
 
 def _empty_results(img_meta, cls_scores):
     ori = dict(img_meta)['ori_shape']
-    return _results(img_meta, cls_scores.new_ones(0), cls_scores.new_ones(0), cls_scores.new_zeros(0, *ori[:2]))
+    r = _results(img_meta, cls_scores.new_ones(0), cls_scores.new_ones(0), cls_scores.new_zeros(0, *ori[:2]))
+    r.mask_stats = cls_scores.new_zeros((0, 5), dtype=torch.int32)
+    return r
 
 
 def _seg_tail(seg_preds, cate_labels, cate_scores, strides, featmap_size, img_meta, cfg):
     """box_solov2_head.py:546-590 from the candidates' probabilities on: the block through ``seg_nms``, then the two bilinear resizes
-    and the final threshold of the kept masks in torch."""
-    h, w = dict(img_meta)['img_shape'][:2]
-    ori_shape = dict(img_meta)['ori_shape']
+    and the final threshold of the kept masks in one kernel (``seg_paste``), which also leaves the area and the box of every mask in
+    ``mask_stats``."""
     scores, labels, keep_inds = seg_nms(seg_preds, cate_labels, cate_scores, strides, cfg)
     if keep_inds.numel() == 0:
         return _empty_results(img_meta, cate_scores)
-    up = (featmap_size[0] * 4, featmap_size[1] * 4)
-    kept = F.interpolate(seg_preds[keep_inds].unsqueeze(0), size=up, mode='bilinear')[:, :, :h, :w]
-    masks = F.interpolate(kept, size=tuple(ori_shape[:2]), mode='bilinear').squeeze(0) > cfg_require(cfg, 'mask_thr')
-    return _results(img_meta, scores, labels, masks)
+    return paste_results(_results(img_meta, scores, labels, None), seg_preds, keep_inds, featmap_size, img_meta, cfg_require(cfg, 'mask_thr'))
 
 
 def box_solov2_get_seg_single(cate_preds, seg_preds, featmap_size, img_meta, cfg, seg_num_grids, strides):
     """``BoxSOLOv2Head.get_seg_single`` (box_solov2_head.py:503-590).  ``cate_preds`` [sum(grid^2), classes], ``seg_preds``
     [sum(grid^2), h, w] probabilities, ``seg_num_grids`` / ``strides`` the head's per-level settings.  Returns an object with
-    ``scores``, ``labels``, ``masks`` (bool [n, ori_h, ori_w]) and the image's ``img_shape`` / ``ori_shape``."""
+    ``scores``, ``labels``, ``masks`` (bool [n, ori_h, ori_w]), ``mask_stats`` (int32 [n,5]: area and box of every mask, see ``seg_paste``)
+    and the image's ``img_shape`` / ``ori_shape``."""
     need_cuda(cate_preds=cate_preds, seg_preds=seg_preds)
     assert len(cate_preds) == len(seg_preds)
     inds = cate_preds > cfg_require(cfg, 'score_thr')
