@@ -35,6 +35,9 @@ Public surface (mirrors the reference's for this path):
     multi_scale_deformable_attn        <-> mmcv.ops.multi_scale_deform_attn.MultiScaleDeformableAttnFunction.apply (restated arithmetic)
     multi_scale_deformable_attn_fused  : the same from reference points, raw offsets and raw logits (normaliser and softmax in the kernel)
     MultiScaleDeformableAttention      <-> mmcv's module, the self-attention of Box2Mask's MSDeformAttnPixelDecoder; ATTENTION, build_attention
+    solo_dynamic_masks                 <-> the dynamic 1x1 convolution and sigmoid of DiscoBoxSOLOv2Head.loss / corr_loss (one launch, autograd)
+    solo_dynamic_masks_pair            : the same for the student's and the teacher's maps with one grid_order (the teacher without a backward)
+    solo_candidate_masks               <-> F.conv2d(seg_preds, kernel_preds[rows]).sigmoid() of get_seg_single, the kernel rows read in place
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -53,6 +56,7 @@ from .solo_targets import SoloTargets, box_solov2_targets, parse_solo_head_cfg, 
 from .corr import ObjectBank, SemanticCorrSolver, corr_objects, parse_corr_cfg, superres_T
 from .roi_align import RoIAlign, corr_level, relu_and_l2_norm_feat, roi_align, roi_feat_norm, sigmoid_roi_masks, target_boxes
 from .msda import MultiScaleDeformableAttention, multi_scale_deformable_attn, multi_scale_deformable_attn_fused
+from .solo_conv import solo_candidate_masks, solo_dynamic_masks, solo_dynamic_masks_pair
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -69,5 +73,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'solov2_targets', 'box_solov2_targets', 'solo_cate_loss', 'parse_solo_head_cfg', 'SoloTargets',
            'ObjectBank', 'SemanticCorrSolver', 'superres_T', 'corr_objects', 'parse_corr_cfg',
            'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level',
-           'multi_scale_deformable_attn', 'multi_scale_deformable_attn_fused', 'MultiScaleDeformableAttention', 'ATTENTION', 'build_attention']
+           'multi_scale_deformable_attn', 'multi_scale_deformable_attn_fused', 'MultiScaleDeformableAttention', 'ATTENTION', 'build_attention',
+           'solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks']
 __version__ = '0.1.0'

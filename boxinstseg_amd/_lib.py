@@ -284,6 +284,20 @@ SEG_SIGNATURES = {
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_dconv.h (the dynamic 1x1 mask convolution of the SOLOv2-style heads, training and test time).  A table of its
+# own like the four above: load() applies it under the same duplicate-name check; tests/test_host_solo_conv.py holds it against its header.
+DCONV_MAPS, DCONV_ROWS, DCONV_NONE, DCONV_SIGMOID, DCONV_MAX_LEVELS, DCONV_MAX_E, DCONV_TILE, DCONV_STATUS_BAD_CELL = 0, 1, 0, 1, 8, 1024, 64, 1
+DCONV_HEADERS = ('include/boxinst/boxinst_hip_dconv.h',)
+DCONV_SIGNATURES = {
+    'bxi_solo_dconv_forward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_void_p,
+                                           C.POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_solo_dconv_forward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_solo_dconv_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'bxi_solo_dconv_backward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_void_p,
+                                            C.POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p, C.POINTER(c_void_p), c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+}
+
 # every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
 # applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
 FAMILIES = [
@@ -317,7 +331,8 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
         owner = {}
         for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES),
-                                                   ('msda', MSDA_HEADERS, MSDA_SIGNATURES), ('seg', SEG_HEADERS, SEG_SIGNATURES)]:
+                                                   ('msda', MSDA_HEADERS, MSDA_SIGNATURES), ('seg', SEG_HEADERS, SEG_SIGNATURES),
+                                                   ('dconv', DCONV_HEADERS, DCONV_SIGNATURES)]:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

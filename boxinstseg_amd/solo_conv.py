@@ -1,0 +1,168 @@
+"""The dynamic 1x1 mask convolution of the SOLOv2-style heads (csrc/solo_dconv.hip, include/boxinst/boxinst_hip_dconv.h): the step between
+the training targets and the mask losses, and between the candidates and Matrix NMS.
+
+    solo_dynamic_masks       <-> DiscoBoxSOLOv2Head.loss, discobox_head.py:1180-1246 and the sigmoid at :1275-1279 (corr_loss :936-1022 is the
+                                 same block): kernel_pred.view(E, -1)[:, grid_order], one F.conv2d per (level, image), the cats, the sigmoid
+    solo_dynamic_masks_pair  the student's and the teacher's maps with one grid_order (use_ind_teacher=True), the teacher without a backward
+    solo_candidate_masks     <-> get_seg_single, discobox_head.py:1607-1608: F.conv2d(seg_preds, kernel_preds[rows]).sigmoid()
+
+There is no CPU or PyTorch fallback: CPU tensors raise.  The kernel values are gathered by the library (torch makes no [N,E] copy), the feature of
+an image is read once per call, and all levels and images are one call forward (a small gather of the kernel values into scratch and ONE
+launch for the product) and one call backward (the gather, the main kernel, the reduction of grad_kernel's per-tile sums and the pass that
+writes every element of every gradient map).  Around the call torch concatenates the grid_order entries into one int64 vector and zeroes
+the status word.  DEVIATION: fp32 only -- half-precision tensors are upcast here and the
+masks are fp32 (the reference runs these statements under fp16 autocast); every logit is one fp32 fmaf chain over e ascending.
+"""
+from __future__ import annotations
+
+import types
+
+import torch
+
+from . import _lib
+from ._common import current_stream, need_cuda
+
+__all__ = ['solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks']
+
+
+def _call_forward(plan, feat, maps):
+    lib = _lib.load()
+    dev = feat.device
+    B, E, H, W = feat.shape
+    out = torch.empty((plan.N, H, W), dtype=torch.float32, device=dev)
+    img = torch.empty((plan.N,), dtype=torch.int64, device=dev)
+    ws_bytes = lib.bxi_solo_dconv_forward_workspace_bytes(plan.N, B, E)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check('bxi_solo_dconv_forward_f32', lib.bxi_solo_dconv_forward_f32(
+            feat.data_ptr(), B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps), plan.layout,
+            None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(), img.data_ptr(),
+            plan.status.data_ptr(), ws.data_ptr(), ws_bytes, current_stream(dev)))
+    return out, img
+
+
+class _DynamicMasks(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, plan, feat, *maps):
+        out, img = _call_forward(plan, feat, maps)
+        ctx.plan = plan
+        ctx.save_for_backward(feat, out, *maps)
+        ctx.mark_non_differentiable(img)
+        return out, img
+
+    @staticmethod
+    def backward(ctx, g_out, _g_img):
+        plan = ctx.plan
+        feat, out, *maps = ctx.saved_tensors
+        need_feat, need_maps = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        if not (need_feat or need_maps):
+            return (None, None) + (None,) * len(maps)
+        lib = _lib.load()
+        dev = feat.device
+        B, E, H, W = feat.shape
+        g = g_out.detach().to(torch.float32).contiguous()
+        g_feat = torch.empty_like(feat) if need_feat else None
+        g_maps = [torch.empty_like(m) for m in maps] if need_maps else None
+        ws_bytes = lib.bxi_solo_dconv_backward_workspace_bytes(plan.N, B, E, H, W)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check('bxi_solo_dconv_backward_f32', lib.bxi_solo_dconv_backward_f32(
+                feat.data_ptr(), B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps), plan.layout,
+                None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(),
+                g.data_ptr(), None if g_feat is None else g_feat.data_ptr(),
+                None if g_maps is None else _lib.ptr_array([m.data_ptr() for m in g_maps]), plan.status.data_ptr(), ws.data_ptr(), ws_bytes,
+                current_stream(dev)))
+        grads = [gm if need else None for gm, need in zip(g_maps, ctx.needs_input_grad[2:])] if need_maps else [None] * len(maps)
+        return (None, g_feat, *grads)
+
+
+def _fp32(t):
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.to(torch.float32).contiguous()
+
+
+def _plan(kernel_preds_raw, grid_order, ins_pred, sigmoid, status):
+    """The segment table of one grid_order: counts on the host, the cells as one int64 vector on the device, level-major."""
+    grid_order = getattr(grid_order, 'grid_order', grid_order)
+    maps = list(kernel_preds_raw)
+    need_cuda(ins_pred=ins_pred, **{f'kernel_preds_raw[{l}]': m for l, m in enumerate(maps)})
+    if ins_pred.dim() != 4:
+        raise RuntimeError(f'ins_pred must be [B,E,H,W], got {tuple(ins_pred.shape)}')
+    B, E = int(ins_pred.shape[0]), int(ins_pred.shape[1])
+    L = len(maps)
+    if not 1 <= L <= _lib.DCONV_MAX_LEVELS:
+        raise RuntimeError(f'{L} levels: 1 .. {_lib.DCONV_MAX_LEVELS} are supported')
+    if len(grid_order) != L or any(len(g) != B for g in grid_order):
+        raise RuntimeError(f'grid_order must be [level][image] = [{L}][{B}]')
+    for l, m in enumerate(maps):
+        if m.dim() != 4 or m.shape[0] != B or m.shape[1] != E or m.shape[2] != m.shape[3] or m.device != ins_pred.device:
+            raise RuntimeError(f'kernel_preds_raw[{l}] must be [{B},{E},S,S] on {ins_pred.device}, got {tuple(m.shape)} on {m.device}')
+    flat = [grid_order[l][b].reshape(-1) for l in range(L) for b in range(B)]
+    need_cuda(**{f'grid_order[{i // B}][{i % B}]': g for i, g in enumerate(flat)})
+    counts = [int(g.numel()) for g in flat]
+    N = sum(counts)
+    cells = torch.cat(flat).to(torch.int64).contiguous() if N else None
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=ins_pred.device)
+    return types.SimpleNamespace(layout=_lib.DCONV_MAPS, grids=[int(m.shape[2]) for m in maps], counts=counts, cells=cells, N=N,
+                                 act=_lib.DCONV_SIGMOID if sigmoid else _lib.DCONV_NONE, status=status, L=L, B=B)
+
+
+def _lists(plan, out, img):
+    """The reference's two lists: per level the masks of its images concatenated and their image indices, None for a level without rows."""
+    masks, inds, at = [], [], 0
+    for l in range(plan.L):
+        n = sum(plan.counts[l * plan.B:(l + 1) * plan.B])
+        masks.append(out[at:at + n] if n else None)
+        inds.append(img[at:at + n] if n else None)
+        at += n
+    return masks, inds
+
+
+def _run(plan, kernel_preds_raw, ins_pred):
+    out, img = _DynamicMasks.apply(plan, _fp32(ins_pred), *[_fp32(m) for m in kernel_preds_raw])
+    return _lists(plan, out, img)
+
+
+def solo_dynamic_masks(kernel_preds_raw, grid_order, ins_pred, sigmoid=True, status=None):
+    """The masks of the assigned grid cells.  ``kernel_preds_raw``: a list over levels of [B,E,S,S]; ``grid_order``: ``SoloTargets.grid_order``
+    ([level][image] int64 on the device, sizes known on the host) or the ``SoloTargets`` object; ``ins_pred`` [B,E,H,W].  Returns
+    ``(masks, img_inds)``: per level the fp32 masks [N_l,H,W] of its images concatenated in order (``sigmoid`` of the logits, or the logits) and
+    the int64 image index of every mask on the device, as ``meanfield_forward`` takes it; ``None`` for a level without instances.  All masks are
+    views of one [N,H,W] buffer.  Gradients reach the kernel maps and ``ins_pred`` where they require them: every element of a map gets one,
+    zero for a cell nobody selected and the sum of its rows' for a cell ``grid_order`` names more than once.  A cell outside its map gives the
+    masks of an all-zero kernel and sets ``status[0]`` (int32 [1] on the device, a fresh zero when not given) to 1; nothing reads it back
+    here."""
+    plan = _plan(kernel_preds_raw, grid_order, ins_pred, sigmoid, status)
+    return _run(plan, kernel_preds_raw, ins_pred)
+
+
+def solo_dynamic_masks_pair(s_kernel_preds_raw, t_kernel_preds_raw, grid_order, s_ins_pred, t_ins_pred, sigmoid=True, status=None):
+    """``solo_dynamic_masks`` for the student and for the independent teacher with one ``grid_order``: the call ``loss`` and ``corr_loss``
+    make.  The teacher runs without a backward (its tensors are detached).  Returns ``(s_masks, t_masks, img_inds)``.  Nothing is kept from
+    one call to the next."""
+    plan = _plan(s_kernel_preds_raw, grid_order, s_ins_pred, sigmoid, status)
+    t_plan = _plan(t_kernel_preds_raw, grid_order, t_ins_pred, sigmoid, plan.status)
+    t_plan.cells = plan.cells
+    s_masks, inds = _run(plan, s_kernel_preds_raw, s_ins_pred)
+    with torch.no_grad():
+        t_masks, _ = _run(t_plan, [m.detach() for m in t_kernel_preds_raw], t_ins_pred.detach())
+    return s_masks, t_masks, inds
+
+
+def solo_candidate_masks(seg_pred, kernel_preds, rows=None, sigmoid=True, status=None):
+    """``F.conv2d(seg_pred, kernel_preds[rows].view(I, E, 1, 1)).squeeze(0).sigmoid()`` of get_seg_single: ``seg_pred`` [1,E,h,w] the mask
+    feature, ``kernel_preds`` [sum(grid^2),E] read in place through ``rows`` (int64 [I] on the device, any order, repeats allowed; every row
+    when None).  Returns [I,h,w] fp32 probabilities (logits with ``sigmoid=False``), ready for ``seg_nms``.  No gradient."""
+    need_cuda(seg_pred=seg_pred, kernel_preds=kernel_preds, rows=rows)
+    if seg_pred.dim() != 4 or seg_pred.shape[0] != 1 or kernel_preds.dim() != 2 or kernel_preds.shape[1] != seg_pred.shape[1]:
+        raise RuntimeError(f'seg_pred must be [1,E,h,w] and kernel_preds [rows,E], got {tuple(seg_pred.shape)} and {tuple(kernel_preds.shape)}')
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int64):
+        raise RuntimeError(f'rows must be int64 [I], got {rows.dtype} {tuple(rows.shape)}')
+    n = int(kernel_preds.shape[0]) if rows is None else int(rows.numel())
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=seg_pred.device)
+    plan = types.SimpleNamespace(layout=_lib.DCONV_ROWS, grids=[max(int(kernel_preds.shape[0]), 1)], counts=[n], N=n,
+                                 cells=None if rows is None else rows.contiguous(), act=_lib.DCONV_SIGMOID if sigmoid else _lib.DCONV_NONE,
+                                 status=status, L=1, B=1)
+    out, _ = _call_forward(plan, _fp32(seg_pred.detach()), [_fp32(kernel_preds.detach())])
+    return out
