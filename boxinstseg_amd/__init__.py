@@ -38,6 +38,10 @@ Public surface (mirrors the reference's for this path):
     solo_dynamic_masks                 <-> the dynamic 1x1 convolution and sigmoid of DiscoBoxSOLOv2Head.loss / corr_loss (one launch, autograd)
     solo_dynamic_masks_pair            : the same for the student's and the teacher's maps with one grid_order (the teacher without a backward)
     solo_candidate_masks               <-> F.conv2d(seg_preds, kernel_preds[rows]).sigmoid() of get_seg_single, the kernel rows read in place
+    box2mask_attn_mask, attn_mask_bits <-> the attention mask of Box2MaskHead.forward_head and its repair in forward, as bits (PackedAttnMask), one launch
+    pack_attn_mask                     : an existing bool attention mask [B*M,Q,S] or [Q,S] packed to a PackedAttnMask on the device
+    masked_attention                   : the attention core of torch.nn.MultiheadAttention with that mask, forward and backward, no [Q,S] tensor
+    MultiheadAttention                 <-> mmcv's module, the cross- and self-attention of Box2Mask's transformer decoder; ATTENTION, build_attention
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -57,6 +61,7 @@ from .corr import ObjectBank, SemanticCorrSolver, corr_objects, parse_corr_cfg, 
 from .roi_align import RoIAlign, corr_level, relu_and_l2_norm_feat, roi_align, roi_feat_norm, sigmoid_roi_masks, target_boxes
 from .msda import MultiScaleDeformableAttention, multi_scale_deformable_attn, multi_scale_deformable_attn_fused
 from .solo_conv import solo_candidate_masks, solo_dynamic_masks, solo_dynamic_masks_pair
+from .masked_attn import MultiheadAttention, PackedAttnMask, attn_mask_bits, box2mask_attn_mask, masked_attention, pack_attn_mask
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -74,5 +79,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'ObjectBank', 'SemanticCorrSolver', 'superres_T', 'corr_objects', 'parse_corr_cfg',
            'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level',
            'multi_scale_deformable_attn', 'multi_scale_deformable_attn_fused', 'MultiScaleDeformableAttention', 'ATTENTION', 'build_attention',
-           'solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks']
+           'solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks',
+           'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention']
 __version__ = '0.1.0'

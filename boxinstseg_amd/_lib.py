@@ -298,6 +298,22 @@ DCONV_SIGNATURES = {
                                             c_size_t, c_void_p]),
 }
 
+# include/boxinst/boxinst_hip_attn.h (the masked cross-attention of Box2Mask's transformer decoder: the mask as bits, forward and backward).  A
+# table of its own like the five above: load() applies it under the same duplicate-name check; tests/test_host_masked_attn.py holds it
+# against its header.
+ATTN_SPAN, ATTN_MAX_Q, ATTN_MAX_S, ATTN_MAX_HEADS, ATTN_HEAD_DIMS = 256, 1 << 20, 1 << 24, 65535, (16, 32, 64)
+ATTN_HEADERS = ('include/boxinst/boxinst_hip_attn.h',)
+ATTN_SIGNATURES = {
+    'bxi_attn_mask_bits_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'bxi_attn_pack_mask_u8': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    'bxi_masked_attn_forward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'bxi_masked_attn_forward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_masked_attn_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'bxi_masked_attn_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                             c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # every ABI family, in the order it arrived: (name, its headers relative to the repository root, its signature table).  load()
 # applies the tables; tests/test_abi_families.py holds each against its headers and the library's exports.
 FAMILIES = [
@@ -332,7 +348,8 @@ def load() -> C.CDLL:
         owner = {}
         for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES),
                                                    ('msda', MSDA_HEADERS, MSDA_SIGNATURES), ('seg', SEG_HEADERS, SEG_SIGNATURES),
-                                                   ('dconv', DCONV_HEADERS, DCONV_SIGNATURES)]:
+                                                   ('dconv', DCONV_HEADERS, DCONV_SIGNATURES),
+                                                   ('attn', ATTN_HEADERS, ATTN_SIGNATURES)]:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -117,6 +117,7 @@ def _make_attention():
 
 
 ATTENTION = _make_attention()         # MultiScaleDeformableAttention (mmcv/cnn/bricks/registry.py: ATTENTION)
+# and MultiheadAttention (masked_attn.py): the cross- and self-attention of Box2Mask's transformer decoder
 
 
 def build_head(cfg: dict, default_args: Optional[dict] = None):
