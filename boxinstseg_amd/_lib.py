@@ -223,10 +223,8 @@ SOLO_SIGNATURES = {
                                                c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_corr.h (DiscoBox's cross-image correspondence: bank, retrieval, solver, loss_corr, iiu).  A table of its
-# own, next to FAMILIES: load() applies it and keeps the duplicate-name check across both; tests/test_host_corr.py holds it against its header.
+# include/boxinst/boxinst_hip_corr.h (DiscoBox's cross-image correspondence: bank, retrieval, solver, loss_corr, iiu)
 CORR_FEAT, CORR_MASK, CORR_MAX_OBJS, CORR_MAX_QUEUE = 7, 28, 8, 1024
-CORR_HEADERS = ('include/boxinst/boxinst_hip_corr.h',)
 CORR_SIGNATURES = {
     'bxi_corr_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'bxi_corr_plan_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
@@ -245,10 +243,8 @@ CORR_SIGNATURES = {
     'bxi_corr_cu_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_roi.h (RoIAlign forward / backward and the front of one level of DiscoBox's corr_loss).  A table of its own like
-# CORR_SIGNATURES: load() applies it and keeps the duplicate-name check across all of them; tests/test_host_roi.py holds it against its header.
+# include/boxinst/boxinst_hip_roi.h (RoIAlign forward / backward and the front of one level of DiscoBox's corr_loss)
 ROI_MAX_POOL, ROI_MAX_SAMPLING, ROI_MAX_SIDE, ROI_FUSED_MAX_C, ROI_FEAT, ROI_SIGMOID = 64, 64, 16384, 8192, 7, 1
-ROI_HEADERS = ('include/boxinst/boxinst_hip_roi.h',)
 ROI_SIGNATURES = {
     'bxi_roi_target_boxes_u8': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'bxi_roi_align_forward_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_void_p,
@@ -262,10 +258,8 @@ ROI_SIGNATURES = {
                                                c_void_p, c_size_t, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_msda.h (multi-scale deformable attention, forward and backward).  A table of its own like CORR_SIGNATURES and
-# ROI_SIGNATURES: load() applies it under the same duplicate-name check; tests/test_host_msda.py holds it against its header.
+# include/boxinst/boxinst_hip_msda.h (multi-scale deformable attention, forward and backward)
 MSDA_MAX_LEVELS, MSDA_MAX_POINTS, MSDA_MIN_HEAD_DIM, MSDA_MAX_HEAD_DIM, MSDA_FUSED, MSDA_MAX_CELL_SAMPLES = 8, 8, 8, 64, 1, 1 << 22
-MSDA_HEADERS = ('include/boxinst/boxinst_hip_msda.h',)
 MSDA_SIGNATURES = {
     'bxi_msda_forward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                      c_void_p, c_void_p]),
@@ -274,20 +268,15 @@ MSDA_SIGNATURES = {
                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_seg.h (the final masks of the SOLOv2-style heads: resize, crop, threshold, area and box of the kept candidates).
-# A table of its own like the three above: load() applies it under the same duplicate-name check; tests/test_host_seg_paste.py holds it
-# against its header.
-SEG_HEADERS = ('include/boxinst/boxinst_hip_seg.h',)
+# include/boxinst/boxinst_hip_seg.h (the final masks of the SOLOv2-style heads: resize, crop, threshold, area and box of the kept candidates)
 SEG_SIGNATURES = {
     'bxi_seg_paste_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'bxi_seg_paste_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_dconv.h (the dynamic 1x1 mask convolution of the SOLOv2-style heads, training and test time).  A table of its
-# own like the four above: load() applies it under the same duplicate-name check; tests/test_host_solo_conv.py holds it against its header.
+# include/boxinst/boxinst_hip_dconv.h (the dynamic 1x1 mask convolution of the SOLOv2-style heads, training and test time)
 DCONV_MAPS, DCONV_ROWS, DCONV_NONE, DCONV_SIGMOID, DCONV_MAX_LEVELS, DCONV_MAX_E, DCONV_TILE, DCONV_STATUS_BAD_CELL = 0, 1, 0, 1, 8, 1024, 64, 1
-DCONV_HEADERS = ('include/boxinst/boxinst_hip_dconv.h',)
 DCONV_SIGNATURES = {
     'bxi_solo_dconv_forward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_void_p,
                                            C.POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -298,11 +287,8 @@ DCONV_SIGNATURES = {
                                             c_size_t, c_void_p]),
 }
 
-# include/boxinst/boxinst_hip_attn.h (the masked cross-attention of Box2Mask's transformer decoder: the mask as bits, forward and backward).  A
-# table of its own like the five above: load() applies it under the same duplicate-name check; tests/test_host_masked_attn.py holds it
-# against its header.
+# include/boxinst/boxinst_hip_attn.h (the masked cross-attention of Box2Mask's transformer decoder: the mask as bits, forward and backward)
 ATTN_SPAN, ATTN_MAX_Q, ATTN_MAX_S, ATTN_MAX_HEADS, ATTN_HEAD_DIMS = 256, 1 << 20, 1 << 24, 65535, (16, 32, 64)
-ATTN_HEADERS = ('include/boxinst/boxinst_hip_attn.h',)
 ATTN_SIGNATURES = {
     'bxi_attn_mask_bits_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'bxi_attn_pack_mask_u8': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -323,6 +309,12 @@ FAMILIES = [
     ('det', ('include/boxinst/boxinst_hip_det.h',), DET_SIGNATURES),
     ('fcos', ('include/boxinst/boxinst_hip_fcos.h',), FCOS_SIGNATURES),
     ('solo', ('include/boxinst/boxinst_hip_solo.h',), SOLO_SIGNATURES),
+    ('corr', ('include/boxinst/boxinst_hip_corr.h',), CORR_SIGNATURES),
+    ('roi', ('include/boxinst/boxinst_hip_roi.h',), ROI_SIGNATURES),
+    ('msda', ('include/boxinst/boxinst_hip_msda.h',), MSDA_SIGNATURES),
+    ('seg', ('include/boxinst/boxinst_hip_seg.h',), SEG_SIGNATURES),
+    ('dconv', ('include/boxinst/boxinst_hip_dconv.h',), DCONV_SIGNATURES),
+    ('attn', ('include/boxinst/boxinst_hip_attn.h',), ATTN_SIGNATURES),
 ]
 
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
@@ -346,10 +338,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in list(FAMILIES) + [('corr', CORR_HEADERS, CORR_SIGNATURES), ('roi', ROI_HEADERS, ROI_SIGNATURES),
-                                                   ('msda', MSDA_HEADERS, MSDA_SIGNATURES), ('seg', SEG_HEADERS, SEG_SIGNATURES),
-                                                   ('dconv', DCONV_HEADERS, DCONV_SIGNATURES),
-                                                   ('attn', ATTN_HEADERS, ATTN_SIGNATURES)]:
+        for family, _, table in FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')
@@ -378,6 +367,13 @@ class BoxInstHipError(RuntimeError):
 def check(fn: str, status: int) -> None:
     if status != 0:
         raise BoxInstHipError(fn, status)
+
+
+def check_supported(fn: str, status: int, header: str) -> None:
+    """check(), except that BXI_ERR_UNSUPPORTED is a NotImplementedError naming the header (of include/boxinst/) that states the support set."""
+    if status == BXI_ERR_UNSUPPORTED:
+        raise NotImplementedError(f'{fn}: outside the support set of include/boxinst/{header}')
+    check(fn, status)
 
 
 def int_array(values) -> C.Array:

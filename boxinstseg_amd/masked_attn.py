@@ -16,6 +16,7 @@ a key_padding_mask, attention dropout in training mode, half precision and CPU t
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -43,10 +44,7 @@ class PackedAttnMask:
         return f'PackedAttnMask(bits={tuple(self.bits.shape)}, S={self.S}, per_head={self.per_head})'
 
 
-def _status(fn, rc):
-    if rc == _lib.BXI_ERR_UNSUPPORTED:
-        raise NotImplementedError(f'{fn}: outside the support set of include/boxinst/boxinst_hip_attn.h')
-    _lib.check(fn, rc)
+_status = functools.partial(_lib.check_supported, header='boxinst_hip_attn.h')
 
 
 def _need_fp32_cuda(**tensors):

@@ -10,6 +10,7 @@ Level 3i).  Thin marshalling only: there is no CPU and no torch path for the sam
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import torch
@@ -68,10 +69,7 @@ def _unsupported(M, D, L, P):
             f'{_lib.MSDA_MAX_HEAD_DIM}, 1..{_lib.MSDA_MAX_LEVELS} levels and 1..{_lib.MSDA_MAX_POINTS} points; got D={D}, L={L}, P={P}')
 
 
-def _status(fn, rc):
-    if rc == _lib.BXI_ERR_UNSUPPORTED:
-        raise NotImplementedError(f'{fn}: outside the support set of include/boxinst/boxinst_hip_msda.h')
-    _lib.check(fn, rc)
+_status = functools.partial(_lib.check_supported, header='boxinst_hip_msda.h')
 
 
 class _MSDA(torch.autograd.Function):

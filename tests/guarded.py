@@ -12,6 +12,9 @@ behind it, often still holding the previous call's (right) answer.  The helpers 
   check_bands(g)                 both bands still hold the poison, bit for bit: nothing was stored outside the tensor.
   check_written(g)               no float / int32 element of the interior still carries the pattern; a uint8 mask is 0 / 1 only.
   check_unchanged(g)             an input's interior is bit-identical to what went in.
+  stream(dev), ptr(x), ok(rc)    what a direct library call needs: the current stream's handle, the address of None / a Guarded / a
+                                 tensor, and `rc == 0` with the status' name.
+  same(got, want)                bit-for-bit equality: NaN payloads and signed zeros count, for every float width.
   poisoned_empty()               torch.empty / torch.empty_like / Tensor.new_empty hand out pattern-filled memory for the duration:
                                  a kernel that leaves an element of its output unwritten, or that depends on what it finds in its
                                  scratch, cannot hide behind a block the allocator recycled.
@@ -169,6 +172,28 @@ def check_unchanged(*gs: Guarded) -> None:
     for g in gs:
         assert g.is_input and g.before is not None
         assert torch.equal(_as_int(g.interior()), _as_int(g.before)), f'an input of shape {tuple(g.t.shape)} was modified'
+
+
+def stream(dev) -> int:
+    """The handle of the current stream of `dev`, as the entry points take it."""
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def ptr(x):
+    """The address a library call gets for None, a Guarded or a tensor."""
+    return None if x is None else x.ptr() if isinstance(x, Guarded) else x.data_ptr()
+
+
+def ok(rc: int) -> None:
+    from boxinstseg_amd import _lib
+    assert rc == 0, _lib.STATUS.get(rc, rc)
+
+
+def same(got: torch.Tensor, want: torch.Tensor) -> bool:
+    """Bit for bit: floats of any width through their integer view, so that NaN payloads and signed zeros count; the rest by torch.equal."""
+    if got.is_floating_point() or want.is_floating_point():
+        return got.dtype == want.dtype and torch.equal(_as_int(got.contiguous()), _as_int(want.contiguous()))
+    return torch.equal(got, want)
 
 
 @contextlib.contextmanager

@@ -43,10 +43,6 @@ GUARDED = {
 }
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 class _Hook:
     """Kernel names of the launches inside the block (bxi_dev_set_launch_hook)."""
 
@@ -99,12 +95,12 @@ def test_pairwise_forward_guarded(dev, dtype, tol, shape, dil):
     band = G.plane_band(H, W, dil)
     xt = torch.from_numpy(x[:, None]).to(dev)
     plain = torch.empty((N, 8, H, W), dtype=xt.dtype, device=dev)
-    assert fn(xt.data_ptr(), N, H, W, 3, dil, plain.data_ptr(), _stream(dev)) == 0
+    assert fn(xt.data_ptr(), N, H, W, 3, dil, plain.data_ptr(), G.stream(dev)) == 0
     leads = [(0, 0), (1, 0), (0, 1), (2, 0), (0, 3), (1, 3)] if dtype == np.float32 else [(0, 0), (1, 0), (0, 1), (1, 1)]
     for lx, lo in leads:
         gx = G.embed(xt, lx, band)
         go = G.out((N, 8, H, W), xt.dtype, dev, lo, band)
-        assert fn(gx.ptr(), N, H, W, 3, dil, go.ptr(), _stream(dev)) == 0, (lx, lo)
+        assert fn(gx.ptr(), N, H, W, 3, dil, go.ptr(), G.stream(dev)) == 0, (lx, lo)
         G.check_bands(gx, go)
         G.check_written(go)
         G.check_unchanged(gx)
@@ -129,7 +125,7 @@ def test_pairwise_backward_guarded(dev, dtype, tol, shape, dil):
     xt, pwt, gpt = torch.from_numpy(x[:, None]).to(dev), torch.from_numpy(pw).to(dev), torch.from_numpy(gp).to(dev)
     ity = torch.int32 if dtype == np.float32 else torch.int64
     plain = torch.empty_like(xt)
-    assert fn(xt.data_ptr(), pwt.data_ptr(), gpt.data_ptr(), N, H, W, 3, dil, plain.data_ptr(), _stream(dev)) == 0
+    assert fn(xt.data_ptr(), pwt.data_ptr(), gpt.data_ptr(), N, H, W, 3, dil, plain.data_ptr(), G.stream(dev)) == 0
     if dtype == np.float32:
         leads = [(0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1), (0, 0, 0, 2), (3, 0, 0, 0), (1, 2, 3, 1)]
     else:
@@ -137,7 +133,7 @@ def test_pairwise_backward_guarded(dev, dtype, tol, shape, dil):
     for lx, lp, lg, lo in leads:
         gx, gpw, ggp = G.embed(xt, lx, band), G.embed(pwt, lp, band), G.embed(gpt, lg, band)
         go = G.out(xt.shape, xt.dtype, dev, lo, band)
-        assert fn(gx.ptr(), gpw.ptr(), ggp.ptr(), N, H, W, 3, dil, go.ptr(), _stream(dev)) == 0
+        assert fn(gx.ptr(), gpw.ptr(), ggp.ptr(), N, H, W, 3, dil, go.ptr(), G.stream(dev)) == 0
         G.check_bands(gx, gpw, ggp, go)
         G.check_written(go)
         G.check_unchanged(gx, gpw, ggp)
@@ -202,7 +198,7 @@ class _EvalSet:
         self.state = G.out(lib.bxi_boxinst_loss_state_bytes(N, h, w), torch.uint8, dev, 0, 1024)       # 256-byte aligned by contract
         self.ws = G.out(lib.bxi_boxinst_eval_workspace_bytes(d['B'], d['H'], d['W'], d['stride'], N_ws or N), torch.uint8, dev, 0, 1024)
         # zeroed once, inside its bands, by the entry point the header names for it
-        rc = lib.bxi_boxinst_eval_workspace_init(self.ws.ptr(), self.ws.numel, _stream(dev))
+        rc = lib.bxi_boxinst_eval_workspace_init(self.ws.ptr(), self.ws.numel, G.stream(dev))
         assert rc == 0, rc
         G.check_bands(self.ws)
         assert int(self.ws.t.ne(0).sum()) == 0
@@ -248,7 +244,7 @@ def test_eval_guarded(dev, canvas, form):
     d = _canvas(canvas)
     ref1 = oracle_path(d, warmup=0.37, want_targets=False)
     ref2 = oracle_path(d, warmup=0.37, g_prj=0.5, g_pw=3.0, want_targets=False)
-    st = _stream(dev)
+    st = G.stream(dev)
 
     def evaluate(s, up):
         if form == 'targets_ahead':
@@ -321,7 +317,7 @@ def test_loss_from_bits_guarded(dev, canvas):
     lib = _lib.load()
     d = _canvas(canvas)
     ref = oracle_path(d, warmup=0.37, g_prj=0.5, g_pw=3.0, want_targets=False)
-    st = _stream(dev)
+    st = G.stream(dev)
     _, bits0, _ = color_affinity(torch.from_numpy(d['imgs']).to(dev), d['img_metas'], want_similarity=False)
     results = {}
     for name, leads in {'aligned': {}, 'logits': dict(logits=1), 'g_logits': dict(g_logits=3), 'bits': dict(bits=5), 'gt_inds': dict(gt_inds=1),
@@ -384,7 +380,7 @@ def test_color_affinity_guarded(dev, canvas):
         lab, sim = G.out((B, 3, h, w), torch.float32, dev, ll, band), G.out((B, 8, h, w), torch.float32, dev, ls, band)
         bits = G.out((B, h, w), torch.uint8, dev, lb, band)
         with _Hook() as hk:
-            rc = lib.bxi_color_affinity_f32(C.byref(batch.struct), stride, 3, 2, 0.3, lab.ptr(), None, sim.ptr(), bits.ptr(), _stream(dev))
+            rc = lib.bxi_color_affinity_f32(C.byref(batch.struct), stride, 3, 2, 0.3, lab.ptr(), None, sim.ptr(), bits.ptr(), G.stream(dev))
         assert rc == 0, _lib.status_string(rc)
         assert set(hk.names) == {'pool_rgb', 'affinity'}, hk.names
         G.check_bands(gi, lab, sim, bits)
@@ -424,7 +420,7 @@ def test_box_bitmasks_guarded(dev):
             views = [gb.t[0:5], gb.t[5:5], gb.t[5:6]]
             ptrs = _lib.ptr_array(v.data_ptr() if v.numel() else 0 for v in views)
             go = G.out((len(allb), h, w), torch.float32, dev, lo, G.plane_band(h, w, 0))
-            rc = lib.bxi_box_bitmasks_f32(C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(cnt, C.POINTER(C.c_int)), 3, H, W, stride, start, go.ptr(), _stream(dev))
+            rc = lib.bxi_box_bitmasks_f32(C.cast(ptrs, C.POINTER(C.c_void_p)), C.cast(cnt, C.POINTER(C.c_int)), 3, H, W, stride, start, go.ptr(), G.stream(dev))
             assert rc == 0, _lib.status_string(rc)
             G.check_bands(gb, go)
             G.check_written(go)
@@ -462,13 +458,13 @@ def test_mask_paste_guarded(dev, out_w):
     plain = torch.empty(total, dtype=torch.uint8, device=dev)
     img_t, off_t = torch.from_numpy(img).to(dev), torch.from_numpy(offs).to(dev)
     assert lib.bxi_mask_paste_u8(logits0.data_ptr(), len(img), h, w, factor, img_t.data_ptr(), off_t.data_ptr(), 2, dims_host, 0.5, plain.data_ptr(),
-                                 _stream(dev)) == 0
+                                 G.stream(dev)) == 0
     cases = [(0, lm, 0) for lm in range(16)] + [(1, 0, 0), (2, 5, 0), (3, 0, 0), (0, 0, 1), (3, 9, 1)]
     for ll, lm, li in cases:
         gl = G.embed(logits0, ll, G.plane_band(h, w, 0))
         gi, gofs = G.embed(img_t, li, 64), G.embed(off_t, li, 64)
         gm = G.out(total, torch.uint8, dev, lm, 1024)
-        rc = lib.bxi_mask_paste_u8(gl.ptr(), len(img), h, w, factor, gi.ptr(), gofs.ptr(), 2, dims_host, 0.5, gm.ptr(), _stream(dev))
+        rc = lib.bxi_mask_paste_u8(gl.ptr(), len(img), h, w, factor, gi.ptr(), gofs.ptr(), 2, dims_host, 0.5, gm.ptr(), G.stream(dev))
         assert rc == 0, _lib.status_string(rc)
         G.check_bands(gl, gi, gofs, gm)
         G.check_written(gm)
@@ -506,7 +502,7 @@ def test_levelset_guarded(dev, N, H, W, Cc):
     lw, gm, gT = lo.levelset_loss(ms, T, pn, 5.0)
     g4 = gl[:, None, None, None]
     band = G.plane_band(H, W)
-    st = _stream(dev)
+    st = G.stream(dev)
     t = lambda a: torch.from_numpy(a).to(dev)
     state_bytes = max(lib.bxi_levelset_state_bytes(N, Cc), 16)
     plain = None

@@ -13,7 +13,7 @@ from tests import masked_attn_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_masked_attn.py checks the table against _lib.ATTN_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.ATTN_SIGNATURES)
 GUARDED = {
     'bxi_attn_mask_bits_f32': 'test_mask_bits_guarded',
     'bxi_attn_pack_mask_u8': 'test_pack_mask_guarded',
@@ -22,23 +22,6 @@ GUARDED = {
 }
 B_, M_ = 2, 2
 SHAPES = [(37, 300, 32), (33, 70, 16), (5, 257, 64)]                 # (Q, S, D): two spans with a tail, one span, every head dimension
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _same(got, want):
-    return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
-
-
-def _ok(rc):
-    from boxinstseg_amd import _lib
-    assert rc == 0, _lib.STATUS.get(rc, rc)
-
-
-def _p(x):
-    return None if x is None else (x.ptr() if isinstance(x, G.Guarded) else x.data_ptr())
 
 
 def _inputs(shape, dev, per_head):
@@ -57,9 +40,9 @@ def test_mask_bits_guarded(dev, lead):
     for h, w in ((5, 7), (32, 32), (96, 80)):
         words = (h * w + 31) // 32
         want = torch.empty((2, 5, words), dtype=torch.int32, device=dev)
-        _ok(lib.bxi_attn_mask_bits_f32(pred.data_ptr(), 2, 5, 64, 64, h, w, want.data_ptr(), _stream(dev)))
+        G.ok(lib.bxi_attn_mask_bits_f32(pred.data_ptr(), 2, 5, 64, 64, h, w, want.data_ptr(), G.stream(dev)))
         gp, out = G.embed(pred, lead), G.out((2, 5, words), torch.int32, dev, 4 - lead)
-        _ok(lib.bxi_attn_mask_bits_f32(gp.ptr(), 2, 5, 64, 64, h, w, out.ptr(), _stream(dev)))
+        G.ok(lib.bxi_attn_mask_bits_f32(gp.ptr(), 2, 5, 64, 64, h, w, out.ptr(), G.stream(dev)))
         G.check_bands(gp, out)
         G.check_written(out)
         G.check_unchanged(gp)
@@ -75,7 +58,7 @@ def test_pack_mask_guarded(dev, lead):
         mask = (torch.rand(rows, S, generator=gen) < 0.5).to(torch.uint8).to(dev)
         words = (S + 31) // 32
         gm, out = G.embed(mask, lead, poison=0xFF), G.out((rows, words), torch.int32, dev, lead)
-        _ok(lib.bxi_attn_pack_mask_u8(gm.ptr(), rows, S, out.ptr(), _stream(dev)))
+        G.ok(lib.bxi_attn_pack_mask_u8(gm.ptr(), rows, S, out.ptr(), G.stream(dev)))
         G.check_bands(gm, out)
         G.check_written(out)
         G.check_unchanged(gm)
@@ -94,8 +77,8 @@ def test_forward_guarded(dev, shape, per_head, lead):
     assert nbytes > 0 and nbytes % 4 == 0
 
     def call(q_, k_, v_, b_, out, lse, ws):
-        _ok(lib.bxi_masked_attn_forward_f32(_p(q_), _p(k_), _p(v_), _p(b_), per_head, B_, M_, Q, S, D, D ** -0.5, _p(out), _p(lse), _p(ws), nbytes,
-                                            _stream(dev)))
+        G.ok(lib.bxi_masked_attn_forward_f32(G.ptr(q_), G.ptr(k_), G.ptr(v_), G.ptr(b_), per_head, B_, M_, Q, S, D, D ** -0.5, G.ptr(out), G.ptr(lse),
+                                             G.ptr(ws), nbytes, G.stream(dev)))
 
     want = [torch.empty((Q, B_, M_ * D), device=dev), torch.empty((B_, M_, Q), device=dev)]
     call(q, k, v, bits, *want, torch.empty(nbytes, dtype=torch.uint8, device=dev))
@@ -106,7 +89,7 @@ def test_forward_guarded(dev, shape, per_head, lead):
     G.check_bands(gq, gk, gv, gb, out, lse, ws)
     G.check_written(out, lse, ws)
     G.check_unchanged(gq, gk, gv, gb)
-    assert _same(out.t, want[0]) and _same(lse.t, want[1]) and bool(torch.isfinite(out.t).all()) and bool(torch.isfinite(lse.t).all())
+    assert G.same(out.t, want[0]) and G.same(lse.t, want[1]) and bool(torch.isfinite(out.t).all()) and bool(torch.isfinite(lse.t).all())
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -120,14 +103,14 @@ def test_backward_guarded(dev, shape, per_head, lead):
     scale = D ** -0.5
     out, lse = torch.empty((Q, B_, M_ * D), device=dev), torch.empty((B_, M_, Q), device=dev)
     fbytes = lib.bxi_masked_attn_forward_workspace_bytes(B_, M_, Q, S, D)
-    _ok(lib.bxi_masked_attn_forward_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), bits.data_ptr(), per_head, B_, M_, Q, S, D, scale, out.data_ptr(),
-                                        lse.data_ptr(), torch.empty(fbytes, dtype=torch.uint8, device=dev).data_ptr(), fbytes, _stream(dev)))
+    G.ok(lib.bxi_masked_attn_forward_f32(q.data_ptr(), k.data_ptr(), v.data_ptr(), bits.data_ptr(), per_head, B_, M_, Q, S, D, scale, out.data_ptr(),
+                                         lse.data_ptr(), torch.empty(fbytes, dtype=torch.uint8, device=dev).data_ptr(), fbytes, G.stream(dev)))
     nbytes = lib.bxi_masked_attn_backward_workspace_bytes(B_, M_, Q, S, D)
     assert nbytes > 0 and nbytes % 4 == 0
 
     def call(g_, q_, k_, v_, b_, o_, l_, dq, dk, dv, ws):
-        _ok(lib.bxi_masked_attn_backward_f32(_p(g_), _p(q_), _p(k_), _p(v_), _p(b_), per_head, _p(o_), _p(l_), B_, M_, Q, S, D, scale, _p(dq), _p(dk),
-                                             _p(dv), _p(ws), nbytes, _stream(dev)))
+        G.ok(lib.bxi_masked_attn_backward_f32(G.ptr(g_), G.ptr(q_), G.ptr(k_), G.ptr(v_), G.ptr(b_), per_head, G.ptr(o_), G.ptr(l_), B_, M_, Q, S, D, scale,
+                                              G.ptr(dq), G.ptr(dk), G.ptr(dv), G.ptr(ws), nbytes, G.stream(dev)))
 
     want = [torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)]
     call(g, q, k, v, bits, out, lse, *want, torch.empty(nbytes, dtype=torch.uint8, device=dev))
@@ -139,4 +122,4 @@ def test_backward_guarded(dev, shape, per_head, lead):
     G.check_written(*outs, ws)                                        # delta and every span's share of dq fill the workspace
     G.check_unchanged(*ins)
     for got, exp in zip(outs, want):
-        assert _same(got.t, exp) and bool(torch.isfinite(got.t).all())
+        assert G.same(got.t, exp) and bool(torch.isfinite(got.t).all())

@@ -26,16 +26,6 @@ MAPS = ('cls', 'bbox', 'ctr')
 B_IMGS, C = 2, SPEC['num_classes']
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _same(got, want):
-    if got.dtype == torch.float32:
-        return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
-    return torch.equal(got, want)
-
-
 def _settings(name):
     from boxinstseg_amd import parse_box_head_cfg
     return parse_box_head_cfg(R.head_cfg(SPEC, name))
@@ -93,13 +83,13 @@ def test_targets_guarded(dev, lead, name):
     rc = _lib.load().bxi_fcos_targets_f32(
         lv, len(SPEC['levels']), B_IMGS, _lib.float_array([v for r in s['regress_ranges'] for v in r]), 1 if s['center_sampling'] else 0,
         s['center_sample_radius'], 1 if s['norm_on_bbox'] else 0, C, gb.ptr(), gl.ptr(), _lib.int_array([0, 5, 7]), *(o.ptr() for o in outs),
-        gw.ptr(), nbytes, _stream(dev))
+        gw.ptr(), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gb, gl, gw, *outs)
     G.check_written(gw, *outs)
     G.check_unchanged(gb, gl)
     for got, want in zip(outs, plain):
-        assert _same(got.t, want)
+        assert G.same(got.t, want)
         assert not got.t.dtype.is_floating_point or bool(torch.isfinite(got.t).all())
     assert outs[8].t.cpu().tolist() == [0]
 
@@ -121,7 +111,7 @@ def test_loss_guarded(dev, lead, name):
 
     def call(levels, grads, labels, bt, ct, norm, losses, ws):
         rc = lib.bxi_fcos_loss_f32(levels, n, B_IMGS, C, labels, bt, ct, norm, s['gamma'], s['alpha'], s['loss_weight_cls'], s['loss_weight_bbox'],
-                                   s['loss_weight_centerness'], kind, s['eps'], grads, losses, ws, nbytes, _stream(dev))
+                                   s['loss_weight_centerness'], kind, s['eps'], grads, losses, ws, nbytes, G.stream(dev))
         assert rc == 0, _lib.STATUS.get(rc, rc)
 
     # plain tensors
@@ -148,10 +138,10 @@ def test_loss_guarded(dev, lead, name):
     G.check_bands(*ins, *outs)
     G.check_written(*outs)
     G.check_unchanged(*ins)
-    assert _same(glosses.t, plain_l) and bool(torch.isfinite(glosses.t).all()) and float(glosses.t.min()) > 0
+    assert G.same(glosses.t, plain_l) and bool(torch.isfinite(glosses.t).all()) and float(glosses.t.min()) > 0
     for k in MAPS:
         for got, want in zip(gout[k], plain_g[k]):
-            assert _same(got.t, want) and bool(torch.isfinite(got.t).all())
+            assert G.same(got.t, want) and bool(torch.isfinite(got.t).all())
     assert any(bool((t.t != 0).any()) for t in gout['bbox']) and any(bool((t.t == 0).any()) for t in gout['bbox'])
 
 
@@ -175,7 +165,7 @@ def test_grad_rescale_guarded(dev, lead, in_place):
     else:
         gin = {k: [G.embed(t, (lead + j) % 4, BAND) for t in maps[k]] for j, k in enumerate(MAPS)}
         gout = {k: [G.out(tuple(t.shape), torch.float32, dev, (lead + 2 + j) % 4, BAND) for t in maps[k]] for j, k in enumerate(MAPS)}
-    rc = lib.bxi_fcos_grad_rescale_f32(_fcos_levels(), n, B_IMGS, C, _grads_array(gin), gup.ptr(), _grads_array(gout), _stream(dev))
+    rc = lib.bxi_fcos_grad_rescale_f32(_fcos_levels(), n, B_IMGS, C, _grads_array(gin), gup.ptr(), _grads_array(gout), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     outs = [t for k in MAPS for t in gout[k]]
     G.check_bands(gup, *outs)
@@ -187,4 +177,4 @@ def test_grad_rescale_guarded(dev, lead, in_place):
         G.check_unchanged(*ins)
     for i, k in enumerate(MAPS):
         for got, src in zip(gout[k], maps[k]):
-            assert _same(got.t, src * up[i])
+            assert G.same(got.t, src * up[i])

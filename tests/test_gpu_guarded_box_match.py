@@ -22,16 +22,8 @@ GUARDED = {
 }
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _same(got, want):
-    return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
 
 
 def _proj_outs(n, H, W, dev, lead):
@@ -56,12 +48,12 @@ def test_project_pred_guarded(dev, shape, lead):
         plain = project_pred(logits, (H, W), bool(act))
         gl = G.embed(logits, lead, G.plane_band(h, w))
         gr, gc, gs, gw, nbytes = _proj_outs(n, H, W, dev, lead)
-        rc = _lib.load().bxi_match_project_pred_f32(gl.ptr(), n, h, w, H, W, act, gr.ptr(), gc.ptr(), gs.ptr(), gw.ptr(), nbytes, _stream(dev))
+        rc = _lib.load().bxi_match_project_pred_f32(gl.ptr(), n, h, w, H, W, act, gr.ptr(), gc.ptr(), gs.ptr(), gw.ptr(), nbytes, G.stream(dev))
         assert rc == 0, _lib.STATUS.get(rc, rc)
         G.check_bands(gl, gr, gc, gs, gw)
         G.check_written(gr, gc, gs, gw)
         G.check_unchanged(gl)
-        assert _same(gr.t, plain[0]) and _same(gc.t, plain[1]) and _same(gs.t, plain[2])
+        assert G.same(gr.t, plain[0]) and G.same(gc.t, plain[1]) and G.same(gs.t, plain[2])
         assert bool(torch.isfinite(gr.t).all()) and bool(torch.isfinite(gc.t).all()) and bool(torch.isfinite(gs.t).all())
 
 
@@ -78,12 +70,12 @@ def test_project_gt_u8_guarded(dev, HW, lead):
     plain = project_gt(masks)
     gm = G.embed(masks, lead, G.plane_band(H, W))
     gr, gc, gs, gw, nbytes = _proj_outs(g, H, W, dev, 1)
-    rc = _lib.load().bxi_match_project_gt_u8(gm.ptr(), g, H, W, gr.ptr(), gc.ptr(), gs.ptr(), gw.ptr(), nbytes, _stream(dev))
+    rc = _lib.load().bxi_match_project_gt_u8(gm.ptr(), g, H, W, gr.ptr(), gc.ptr(), gs.ptr(), gw.ptr(), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gm, gr, gc, gs, gw)
     G.check_written(gr, gc, gs, gw)
     G.check_unchanged(gm)
-    assert _same(gr.t, plain[0]) and _same(gc.t, plain[1]) and _same(gs.t, plain[2])
+    assert G.same(gr.t, plain[0]) and G.same(gc.t, plain[1]) and G.same(gs.t, plain[2])
     assert torch.equal(gr.t, masks.amax(2).float()) and torch.equal(gc.t, masks.amax(1).float()) and float(gr.t.max()) <= 3.0
 
 
@@ -99,12 +91,12 @@ def test_project_gt_f32_guarded(dev, HW, lead):
     plain = project_gt(masks)
     gm = G.embed(masks, lead, G.plane_band(H, W))
     gr, gc, gs, gw, nbytes = _proj_outs(g, H, W, dev, lead)
-    rc = _lib.load().bxi_match_project_gt_f32(gm.ptr(), g, H, W, gr.ptr(), gc.ptr(), gs.ptr(), gw.ptr(), nbytes, _stream(dev))
+    rc = _lib.load().bxi_match_project_gt_f32(gm.ptr(), g, H, W, gr.ptr(), gc.ptr(), gs.ptr(), gw.ptr(), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gm, gr, gc, gs, gw)
     G.check_written(gr, gc, gs, gw)
     G.check_unchanged(gm)
-    assert _same(gr.t, plain[0]) and _same(gc.t, plain[1]) and _same(gs.t, plain[2])
+    assert G.same(gr.t, plain[0]) and G.same(gc.t, plain[1]) and G.same(gs.t, plain[2])
     assert torch.equal(gr.t, masks.amax(2)) and torch.equal(gc.t, masks.amax(1))
 
 
@@ -131,12 +123,12 @@ def test_match_cost_guarded(dev, Q, counts):
     gg = [G.embed(t, 3 - k) for k, t in enumerate(d['gt'])]
     gcost, gst = G.out(total * Q, torch.float32, dev, 3), G.out(P, torch.int32, dev, 1)
     rc = _lib.load().bxi_match_cost_f32(gcls.ptr(), C, glab.ptr(), gp[0].ptr(), gp[1].ptr(), gp[2].ptr(), gg[0].ptr(), gg[1].ptr(), gg[2].ptr(),
-                                        P, Q, _lib.int_array(offsets), H, W, 2.0, 5.0, 1.0, gcost.ptr(), gst.ptr(), _stream(dev))
+                                        P, Q, _lib.int_array(offsets), H, W, 2.0, 5.0, 1.0, gcost.ptr(), gst.ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gcls, glab, gcost, gst, *gp, *gg)
     G.check_written(gcost, gst)
     G.check_unchanged(gcls, glab, *gp, *gg)
-    assert _same(gcost.t, plain_cost) and torch.equal(gst.t, plain_status) and gst.t.cpu().tolist() == [0] * P
+    assert G.same(gcost.t, plain_cost) and torch.equal(gst.t, plain_status) and gst.t.cpu().tolist() == [0] * P
     assert bool(torch.isfinite(gcost.t).all())
 
 
@@ -156,7 +148,7 @@ def test_linear_sum_assignment_guarded(dev, Q, counts):
     ggi, gl = G.out((P, Q), torch.int64, dev, 1), G.out((P, Q), torch.int64, dev, 1)
     gpos, gpg, gst = G.out(npos, torch.int64, dev, 1), G.out(npos, torch.int64, dev, 1), G.out(P, torch.int32, dev, 3)
     rc = _lib.load().bxi_linear_sum_assignment_f32(gcost.ptr(), glab.ptr(), P, Q, _lib.int_array(offsets), ggi.ptr(), gl.ptr(), gpos.ptr(),
-                                                   gpg.ptr(), gst.ptr(), _stream(dev))
+                                                   gpg.ptr(), gst.ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gcost, glab, ggi, gl, gpos, gpg, gst)
     G.check_written(ggi, gl, gpos, gpg, gst)

@@ -23,14 +23,6 @@ GUARDED = {
 BAND = 4096          # more than the largest plane of the case (12 x 20) times the channels one over-run could cross
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _same(got, want):
-    return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
-
-
 def _case(dev):
     g = np.load(R.__file__.replace('box_nms_ref.py', 'golden/det_nms.npz'))
     return {k: [torch.from_numpy(g[f'in_{k}{lv}']).to(dev) for lv in range(len(R.DET_SIZES))] for k in ('cls', 'bbox', 'ctr', 'params')}
@@ -55,12 +47,12 @@ def test_location_score_guarded(dev, lead):
     plain = box_nms.location_scores(box_nms._Levels(inp['cls'], inp['bbox'], inp['ctr'], inp['params'], R.DET_STRIDES))
     arr, gs = _guarded_levels(inp, lead)
     out = G.out(tuple(plain.shape), torch.float32, dev, lead)
-    rc = _lib.load().bxi_det_location_score_f32(arr, len(R.DET_SIZES), R.DET_B, R.DET_C, out.ptr(), _stream(dev))
+    rc = _lib.load().bxi_det_location_score_f32(arr, len(R.DET_SIZES), R.DET_B, R.DET_C, out.ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(out, *gs)
     G.check_written(out)
     G.check_unchanged(*gs)
-    assert _same(out.t, plain) and bool(torch.isfinite(out.t).all())
+    assert G.same(out.t, plain) and bool(torch.isfinite(out.t).all())
 
 
 @pytest.mark.parametrize('lead', [1, 3])
@@ -89,7 +81,7 @@ def test_candidates_guarded(dev, lead, with_sel):
     gc, gw = G.out(R.DET_B, torch.int32, dev, 3), G.out(nbytes // 4, torch.int32, dev, lead)
     rc = _lib.load().bxi_det_candidates_f32(arr, len(R.DET_SIZES), R.DET_B, R.DET_C, gsel.ptr() if with_sel else None, M,
                                             _lib.float_array([v for row in dims for v in row]), 1, 0.05, cap, gb.ptr(), gsc.ptr(), gl.ptr(),
-                                            gp.ptr(), gc.ptr(), gw.ptr(), nbytes, _stream(dev))
+                                            gp.ptr(), gc.ptr(), gw.ptr(), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gb, gsc, gl, gp, gc, gw, *gs, *([gsel] if with_sel else []))
     G.check_written(gc, gw)
@@ -97,7 +89,7 @@ def test_candidates_guarded(dev, lead, with_sel):
     assert gc.t.cpu().tolist() == counts
     pattern32 = G.pattern_bits(torch.int32)
     for b, n in enumerate(counts):
-        assert _same(gb.t[b, :n], plain[0][b, :n]) and _same(gsc.t[b, :n], plain[1][b, :n])
+        assert G.same(gb.t[b, :n], plain[0][b, :n]) and G.same(gsc.t[b, :n], plain[1][b, :n])
         assert torch.equal(gl.t[b, :n], plain[2][b, :n]) and torch.equal(gp.t[b, :n], plain[3][b, :n])
         assert bool(torch.isfinite(gb.t[b, :n]).all()) and bool(torch.isfinite(gsc.t[b, :n]).all())
         assert bool((gp.t[b, n:] == pattern32).all()) and bool((gsc.t[b, n:].view(torch.int32) == G.PATTERN_F32).all())   # rows behind count: untouched
@@ -133,7 +125,7 @@ def test_box_nms_guarded(dev, lead, own_sort):
     gk, gn, gst = G.out((P, cap), torch.int32, dev, lead), G.out(P, torch.int32, dev, 1), G.out(P, torch.int32, dev, 3)
     gw = G.out(nbytes // 4, torch.int32, dev, lead, BAND)
     rc = _lib.load().bxi_box_nms_f32(gb.ptr(), gs.ptr(), gl.ptr(), gc.ptr(), None if own_sort else go.ptr(), P, cap, 0.5, 0, -1, gk.ptr(),
-                                     gn.ptr(), gst.ptr(), gw.ptr(), nbytes, _stream(dev))
+                                     gn.ptr(), gst.ptr(), gw.ptr(), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     ins = [gb, gs, gl, gc] + ([] if own_sort else [go])
     G.check_bands(gk, gn, gst, gw, *ins)
@@ -167,7 +159,7 @@ def test_box_nms_guarded_max_num_above_cap(dev, own_sort):
     gk, gn, gst = G.out((P, max_num), torch.int32, dev, lead), G.out(P, torch.int32, dev, 1), G.out(P, torch.int32, dev, 3)
     gw = G.out(nbytes // 4, torch.int32, dev, lead, BAND)
     rc = _lib.load().bxi_box_nms_f32(gb.ptr(), gs.ptr(), gl.ptr(), gc.ptr(), None if own_sort else go.ptr(), P, cap, 0.5, 0, max_num, gk.ptr(),
-                                     gn.ptr(), gst.ptr(), gw.ptr(), nbytes, _stream(dev))
+                                     gn.ptr(), gst.ptr(), gw.ptr(), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     ins = [gb, gs, gl, gc] + ([] if own_sort else [go])
     G.check_bands(gk, gn, gst, gw, *ins)
@@ -202,7 +194,7 @@ def test_gather_guarded(dev, lead):
             G.out((R.DET_B, max_keep), torch.int64, dev, 1)]
     rc = _lib.load().bxi_det_gather_f32(arr, len(R.DET_SIZES), R.DET_B, R.DET_C, R.DET_P, gsel.ptr(), sel.shape[1], gc[0].ptr(), gc[1].ptr(),
                                         gc[2].ptr(), gc[3].ptr(), cap, gk.ptr(), gn.ptr(), max_keep, outs[0].ptr(), outs[1].ptr(), outs[2].ptr(),
-                                        outs[3].ptr(), outs[4].ptr(), _stream(dev))
+                                        outs[3].ptr(), outs[4].ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(*outs, *gs, gsel, gk, gn, *gc)
     G.check_written(*outs)

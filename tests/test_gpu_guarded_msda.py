@@ -12,25 +12,12 @@ from tests import msda_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_msda.py checks the table against _lib.MSDA_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.MSDA_SIGNATURES)
 GUARDED = {
     'bxi_msda_forward_f32': 'test_forward_guarded',
     'bxi_msda_backward_f32': 'test_backward_guarded',
 }
 CASES = ['plain', 'heads_d16_l8_p1', 'heads_d64_l1_p8', 'heads_d8_l1_p1']      # plain, fused, fused, plain: every head dimension
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _same(got, want):
-    return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
-
-
-def _ok(rc):
-    from boxinstseg_amd import _lib
-    assert rc == 0, _lib.STATUS.get(rc, rc)
 
 
 def _inputs(name, dev):
@@ -44,10 +31,6 @@ def _inputs(name, dev):
             dev_t(t['grad_out'])), dims, flags
 
 
-def _p(x):
-    return None if x is None else (x.ptr() if isinstance(x, G.Guarded) else x.data_ptr())
-
-
 @pytest.mark.parametrize('lead', [1, 2, 3])
 @pytest.mark.parametrize('name', CASES)
 def test_forward_guarded(dev, name, lead):
@@ -57,7 +40,7 @@ def test_forward_guarded(dev, name, lead):
     B, S, M, D, Q, L, P = dims
 
     def call(v, s_, l_, a_, o_, w_, out):
-        _ok(lib.bxi_msda_forward_f32(_p(v), _p(s_), _p(l_), _p(a_), _p(o_), _p(w_), B, S, M, D, Q, L, P, flags, _p(out), _stream(dev)))
+        G.ok(lib.bxi_msda_forward_f32(G.ptr(v), G.ptr(s_), G.ptr(l_), G.ptr(a_), G.ptr(o_), G.ptr(w_), B, S, M, D, Q, L, P, flags, G.ptr(out), G.stream(dev)))
 
     want = torch.empty((B, Q, M * D), device=dev)
     call(value, ss, ls, a, off, w, want)
@@ -70,7 +53,7 @@ def test_forward_guarded(dev, name, lead):
     G.check_bands(*ins, out)
     G.check_written(out)
     G.check_unchanged(*ins)
-    assert _same(out.t, want) and bool(torch.isfinite(out.t).all())
+    assert G.same(out.t, want) and bool(torch.isfinite(out.t).all())
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -84,8 +67,8 @@ def test_backward_guarded(dev, name, lead):
     assert nbytes > 0 and nbytes % 16 == 0
 
     def call(g_, v, s_, l_, a_, o_, w_, gv, ga, gw, ws):
-        _ok(lib.bxi_msda_backward_f32(_p(g_), _p(v), _p(s_), _p(l_), _p(a_), _p(o_), _p(w_), B, S, M, D, Q, L, P, flags, _p(gv), _p(ga), _p(gw), _p(ws),
-                                      nbytes, _stream(dev)))
+        G.ok(lib.bxi_msda_backward_f32(G.ptr(g_), G.ptr(v), G.ptr(s_), G.ptr(l_), G.ptr(a_), G.ptr(o_), G.ptr(w_), B, S, M, D, Q, L, P, flags,
+                                       G.ptr(gv), G.ptr(ga), G.ptr(gw), G.ptr(ws), nbytes, G.stream(dev)))
 
     want = [torch.empty((B, S, M, D), device=dev), torch.empty((B, Q, M, L, P, 2), device=dev), torch.empty(tuple(w.shape), device=dev)]
     call(g, value, ss, ls, a, off, w, *want, torch.empty(nbytes, dtype=torch.uint8, device=dev))
@@ -100,4 +83,4 @@ def test_backward_guarded(dev, name, lead):
     G.check_written(*outs, ws)                                                # the partial maxima and the accumulator fill the workspace
     G.check_unchanged(*ins)
     for got, exp in zip(outs, want):
-        assert _same(got.t, exp) and bool(torch.isfinite(got.t).all())
+        assert G.same(got.t, exp) and bool(torch.isfinite(got.t).all())

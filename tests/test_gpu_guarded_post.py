@@ -21,10 +21,6 @@ GUARDED = {
 }
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _t(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
@@ -54,7 +50,7 @@ def test_mask_pack_f32_guarded(dev, hw, lead):
     plain = pack_probs(probs, 0.5)
     gp = G.embed(probs, lead, G.plane_band(h, w))
     gb, ga, gs = G.out((n, _words(h, w)), torch.int64, dev, 1), G.out(n, torch.int32, dev, lead), G.out(n, torch.float32, dev, 4 - lead)
-    rc = lib.bxi_mask_pack_f32(gp.ptr(), n, h, w, 0.5, gb.ptr(), ga.ptr(), gs.ptr(), _stream(dev))
+    rc = lib.bxi_mask_pack_f32(gp.ptr(), n, h, w, 0.5, gb.ptr(), ga.ptr(), gs.ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gp, gb, ga, gs)
     G.check_written(gb, ga, gs)
@@ -76,7 +72,7 @@ def test_mask_pack_u8_guarded(dev, hw, lead):
     plain = pack_masks(masks)
     gm = G.embed(masks, lead, G.plane_band(h, w))
     gb, ga = G.out((n, _words(h, w)), torch.int64, dev, 1), G.out(n, torch.int32, dev, 3)
-    rc = lib.bxi_mask_pack_u8(gm.ptr(), n, h, w, gb.ptr(), ga.ptr(), _stream(dev))
+    rc = lib.bxi_mask_pack_u8(gm.ptr(), n, h, w, gb.ptr(), ga.ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gm, gb, ga)
     G.check_written(gb, ga)
@@ -107,7 +103,7 @@ def test_matrix_nms_guarded(dev, n, n_all, hw, kernel):
     assert ws_bytes % 4 == 0
     gd, gi, gw = G.out(n, torch.float32, dev, 1), G.out((n, n), torch.float32, dev, 3), G.out(ws_bytes // 4, torch.float32, dev, 1)
     rc = lib.bxi_matrix_nms_f32(gbits.ptr(), garea.ptr(), glab.ptr(), gord.ptr(), gsc.ptr(), n_all, n, h, w, kernel, 2.0, gd.ptr(), gi.ptr(),
-                                gw.ptr(), ws_bytes, _stream(dev))
+                                gw.ptr(), ws_bytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gbits, garea, glab, gord, gsc, gd, gi, gw)
     G.check_written(gd, gi, gw)

@@ -12,7 +12,7 @@ from tests import roi_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_roi.py checks the table against _lib.ROI_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.ROI_SIGNATURES)
 GUARDED = {
     'bxi_roi_target_boxes_u8': 'test_target_boxes_guarded',
     'bxi_roi_align_forward_f32': 'test_forward_guarded',
@@ -26,21 +26,6 @@ B_, C_, H_, W_ = (int(s) for s in CASE['feat'].shape)
 BAND = G.plane_band(H_, W_)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _same(got, want):
-    if got.dtype == torch.float32:
-        return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
-    return torch.equal(got, want)
-
-
-def _ok(rc):
-    from boxinstseg_amd import _lib
-    assert rc == 0, _lib.STATUS.get(rc, rc)
-
-
 @pytest.mark.parametrize('lead', [1, 2, 3])
 @pytest.mark.parametrize('own', [0, 1])
 def test_target_boxes_guarded(dev, lead, own):
@@ -51,11 +36,11 @@ def test_target_boxes_guarded(dev, lead, own):
     want = target_boxes(t, labels, bool(own))
     gt, gl = G.embed(t, lead, 1024), G.embed(labels, 1, 1024)
     boxes, keep, lab = G.out((6, 4), torch.float32, dev, lead), G.out(6, torch.uint8, dev, lead), G.out(6, torch.int64, dev, 1)
-    _ok(_lib.load().bxi_roi_target_boxes_u8(gt.ptr(), gl.ptr(), 6, 13, 21, own, boxes.ptr(), keep.ptr(), lab.ptr(), _stream(dev)))
+    G.ok(_lib.load().bxi_roi_target_boxes_u8(gt.ptr(), gl.ptr(), 6, 13, 21, own, boxes.ptr(), keep.ptr(), lab.ptr(), G.stream(dev)))
     G.check_bands(gt, gl, boxes, keep, lab)
     G.check_written(boxes, keep, lab)
     G.check_unchanged(gt, gl)
-    assert _same(boxes.t, want[0]) and torch.equal(keep.t.bool(), want[1]) and torch.equal(lab.t, want[2])
+    assert G.same(boxes.t, want[0]) and torch.equal(keep.t.bool(), want[1]) and torch.equal(lab.t, want[2])
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -68,7 +53,7 @@ def test_forward_guarded(dev, lead, flags):
         K = int(rois.shape[0])
 
         def call(f, r, o):
-            _ok(lib.bxi_roi_align_forward_f32(f, r, B_, C_, H_, W_, K, size[0], size[1], 1.0, sr, aligned, flags, o, _stream(dev)))
+            G.ok(lib.bxi_roi_align_forward_f32(f, r, B_, C_, H_, W_, K, size[0], size[1], 1.0, sr, aligned, flags, o, G.stream(dev)))
 
         want = torch.empty((K, C_) + size, device=dev)
         call(feat.data_ptr(), rois.data_ptr(), want.data_ptr())
@@ -78,7 +63,7 @@ def test_forward_guarded(dev, lead, flags):
         G.check_bands(gf, gr, out)
         G.check_written(out)
         G.check_unchanged(gf, gr)
-        assert _same(out.t, want) and bool(torch.isfinite(out.t).all())
+        assert G.same(out.t, want) and bool(torch.isfinite(out.t).all())
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -91,7 +76,7 @@ def test_backward_guarded(dev, lead):
         g = torch.sin(torch.arange(K * C_ * size[0] * size[1], device=dev, dtype=torch.float32)).view((K, C_) + size)
 
         def call(gp, r, o):
-            _ok(lib.bxi_roi_align_backward_f32(gp, r, B_, C_, H_, W_, K, size[0], size[1], 1.0, sr, aligned, o, _stream(dev)))
+            G.ok(lib.bxi_roi_align_backward_f32(gp, r, B_, C_, H_, W_, K, size[0], size[1], 1.0, sr, aligned, o, G.stream(dev)))
 
         want = torch.empty((B_, C_, H_, W_), device=dev)
         call(g.data_ptr(), rois.data_ptr(), want.data_ptr())
@@ -101,7 +86,7 @@ def test_backward_guarded(dev, lead):
         G.check_bands(gg, gr, out)
         G.check_written(out)
         G.check_unchanged(gg, gr)
-        assert _same(out.t, want) and bool(torch.isfinite(out.t).all())
+        assert G.same(out.t, want) and bool(torch.isfinite(out.t).all())
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -122,15 +107,15 @@ def test_feat_norm_guarded(dev, lead):
     ws = G.out(nbytes // 4, torch.float32, dev, 0, band)                     # 16-byte aligned, exactly the size asked for
     gf, gr = G.embed(feat, lead, band), G.embed(rois, 4 - lead, band)
     out = G.out((K, Cn, 7, 7), torch.float32, dev, lead, band)
-    _ok(lib.bxi_roi_feat_norm_forward_f32(gf.ptr(), gr.ptr(), Bn, Cn, Hn, Wn, K, 1.0, 0, 1, out.ptr(), ws.ptr(), nbytes, _stream(dev)))
+    G.ok(lib.bxi_roi_feat_norm_forward_f32(gf.ptr(), gr.ptr(), Bn, Cn, Hn, Wn, K, 1.0, 0, 1, out.ptr(), ws.ptr(), nbytes, G.stream(dev)))
     G.check_bands(gf, gr, out, ws)
     G.check_written(out)
     G.check_unchanged(gf, gr)
-    assert _same(out.t, want.detach())
+    assert G.same(out.t, want.detach())
     go, gg = G.embed(out.t.clone(), 4 - lead, band), G.embed(g, lead, band)
     gin = G.out((Bn, Cn, Hn, Wn), torch.float32, dev, 4 - lead, band)
-    _ok(lib.bxi_roi_feat_norm_backward_f32(go.ptr(), gg.ptr(), gr.ptr(), Bn, Cn, Hn, Wn, K, 1.0, 0, 1, gin.ptr(), ws.ptr(), nbytes, _stream(dev)))
+    G.ok(lib.bxi_roi_feat_norm_backward_f32(go.ptr(), gg.ptr(), gr.ptr(), Bn, Cn, Hn, Wn, K, 1.0, 0, 1, gin.ptr(), ws.ptr(), nbytes, G.stream(dev)))
     G.check_bands(go, gg, gr, gin, ws)
     G.check_written(gin, ws)                                                 # the norms and the pooled gradients fill the workspace
     G.check_unchanged(go, gg, gr)
-    assert _same(gin.t, x.grad) and bool(torch.isfinite(gin.t).all())
+    assert G.same(gin.t, x.grad) and bool(torch.isfinite(gin.t).all())

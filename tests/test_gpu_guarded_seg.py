@@ -14,7 +14,7 @@ from tests import matrix_nms_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_seg_paste.py checks the table against _lib.SEG_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.SEG_SIGNATURES)
 GUARDED = {
     'bxi_seg_paste_u8': 'test_seg_paste_guarded',
 }
@@ -22,15 +22,10 @@ HW, CROP = (13, 21), (50, 81)
 KEEP = [4, 0, -1, 2, 2, 5]                                   # a repeat and two indices outside [0, 5)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _call(lib, dev, probs, keep, out, masks, stats, ws, nbytes):
     from boxinstseg_amd import _lib
-    p = lambda x: x.ptr() if isinstance(x, G.Guarded) else x.data_ptr()  # noqa: E731
-    rc = lib.bxi_seg_paste_u8(p(probs), 5, HW[0], HW[1], p(keep), len(KEEP), 4 * HW[0], 4 * HW[1], CROP[0], CROP[1], out[0], out[1], 0.5,
-                              p(masks), p(stats), p(ws), nbytes, _stream(dev))
+    rc = lib.bxi_seg_paste_u8(G.ptr(probs), 5, HW[0], HW[1], G.ptr(keep), len(KEEP), 4 * HW[0], 4 * HW[1], CROP[0], CROP[1], out[0], out[1], 0.5,
+                              G.ptr(masks), G.ptr(stats), G.ptr(ws), nbytes, G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
 
 

@@ -15,7 +15,7 @@ from tests import solo_conv_ref as R
 
 pytestmark = pytest.mark.gpu
 
-# entry point -> the test that runs it guarded (tests/test_host_solo_conv.py checks the table against _lib.DCONV_SIGNATURES)
+# entry point -> the test that runs it guarded (tests/test_abi_families.py checks the table against _lib.DCONV_SIGNATURES)
 GUARDED = {
     'bxi_solo_dconv_forward_f32': 'test_forward_guarded',
     'bxi_solo_dconv_backward_f32': 'test_backward_guarded',
@@ -24,22 +24,18 @@ H, W = 13, 21
 GRIDS, COUNTS = [3, 2], [[3, 0, 2], [1, 0, 34]]               # an image without rows; 36 rows in image 2: a second chunk of 32
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _call(lib, dev, which, layout, E, feat, maps, cells, counts, act, out, img, status, ws, nbytes, gout=None, gfeat=None, gmaps=None):
     from boxinstseg_amd import _lib
-    p = lambda x: None if x is None else (x.ptr() if isinstance(x, G.Guarded) else x.data_ptr())          # noqa: E731
     B = 1 if layout else 3
     grids = [maps[0].t.shape[0] if isinstance(maps[0], G.Guarded) else maps[0].shape[0]] if layout else GRIDS
-    head = (p(feat), B, E, H, W, _lib.ptr_array([p(m) for m in maps]), _lib.int_array(grids), len(maps), layout, p(cells), _lib.int_array(counts),
-            sum(counts), act)
+    head = (G.ptr(feat), B, E, H, W, _lib.ptr_array([G.ptr(m) for m in maps]), _lib.int_array(grids), len(maps), layout, G.ptr(cells),
+            _lib.int_array(counts), sum(counts), act)
     if which == 'forward':
-        rc = lib.bxi_solo_dconv_forward_f32(*head, p(out), p(img), p(status), p(ws), nbytes, _stream(dev))
+        rc = lib.bxi_solo_dconv_forward_f32(*head, G.ptr(out), G.ptr(img), G.ptr(status), G.ptr(ws), nbytes, G.stream(dev))
     else:
-        rc = lib.bxi_solo_dconv_backward_f32(*head, p(out), p(gout), p(gfeat), None if gmaps is None else _lib.ptr_array([p(m) for m in gmaps]),
-                                             p(status), p(ws), nbytes, _stream(dev))
+        rc = lib.bxi_solo_dconv_backward_f32(*head, G.ptr(out), G.ptr(gout), G.ptr(gfeat),
+                                             None if gmaps is None else _lib.ptr_array([G.ptr(m) for m in gmaps]), G.ptr(status), G.ptr(ws), nbytes,
+                                             G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
 
 

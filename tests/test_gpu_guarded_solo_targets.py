@@ -27,16 +27,6 @@ L, B_IMGS, C = len(SPEC['num_grids']), SPEC['B'], SPEC['num_classes']
 OFFSETS = [0, 6, 8, 8]
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _same(got, want):
-    if got.dtype == torch.float32:
-        return torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
-    return torch.equal(got, want)
-
-
 def _plain(dev, mode):
     import boxinstseg_amd as B
     from boxinstseg_amd import parse_solo_head_cfg
@@ -64,14 +54,14 @@ def test_mask_pass_guarded(dev, lead):
     rc = _lib.load().bxi_solo_mask_pass_u8(
         pa([gm[0].ptr(), gm[1].ptr(), 0]), ia(OFFSETS), ia([64, 32, 32]), ia([96, 64, 32]), B_IMGS, ia(factors),
         ia([plain.masks[f].shape[1] for f in factors]), ia([plain.masks[f].shape[2] for f in factors]), len(factors), pa([o.ptr() for o in gout]),
-        gmom.ptr(), _stream(dev))
+        gmom.ptr(), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(*gm, *gout, gmom)
     G.check_written(*gout, gmom)
     G.check_unchanged(*gm)
-    assert _same(gmom.t, plain.moments)
+    assert G.same(gmom.t, plain.moments)
     for o, f in zip(gout, factors):
-        assert _same(o.t, plain.masks[f]), f
+        assert G.same(o.t, plain.masks[f]), f
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -91,24 +81,24 @@ def test_assign_guarded(dev, lead, mode):
     h, w = SPEC['mask_feat_size']
     rc = _lib.load().bxi_solo_assign_f32(
         _lib.SOLO_MODES[mode], B_IMGS, L, _lib.int_array(s['num_grids']), _lib.float_array([v for r in s['scale_ranges'] for v in r]), s['sigma'],
-        C, 4 * h, 4 * w, gb.ptr(), gl.ptr(), gmo.ptr(), _lib.int_array(OFFSETS), *(o.ptr() for o in outs), _stream(dev))
+        C, 4 * h, 4 * w, gb.ptr(), gl.ptr(), gmo.ptr(), _lib.int_array(OFFSETS), *(o.ptr() for o in outs), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gb, gl, gmo, *outs)
     G.check_written(*outs)
     G.check_unchanged(gb, gl, gmo)
     cate, ind, owner, sel, pc, pi, counts, num_ins, status = (o.t for o in outs)
-    assert _same(cate, plain.flat_cate_labels) and _same(ind.bool(), torch.cat(plain.ins_ind_labels)) and _same(owner, torch.cat(plain.cell_owner))
-    assert counts.view(L, B_IMGS, 2).cpu().tolist() == plain.counts and _same(num_ins, plain.num_ins) and status.cpu().tolist() == [0]
+    assert G.same(cate, plain.flat_cate_labels) and G.same(ind.bool(), torch.cat(plain.ins_ind_labels)) and G.same(owner, torch.cat(plain.cell_owner))
+    assert counts.view(L, B_IMGS, 2).cpu().tolist() == plain.counts and G.same(num_ins, plain.num_ins) and status.cpu().tolist() == [0]
     at = 0
     for l, S in enumerate(s['num_grids']):
         for b in range(B_IMGS):
             p0, (np_, ns) = _lib.SOLO_PAIRS_PER_INSTANCE * (l * 8 + OFFSETS[b]), plain.counts[l][b]
             cap = _lib.SOLO_PAIRS_PER_INSTANCE * (OFFSETS[b + 1] - OFFSETS[b])
-            assert _same(pc[p0:p0 + np_].long(), plain.grid_order[l][b]) and bool((pc[p0 + np_:p0 + cap] == -1).all())
+            assert G.same(pc[p0:p0 + np_].long(), plain.grid_order[l][b]) and bool((pc[p0 + np_:p0 + cap] == -1).all())
             assert bool((pi[p0 + np_:p0 + cap] == -1).all()) and bool((sel[at + ns:at + S * S] == -1).all())
             at += S * S
-        assert _same(torch.cat([pi[_lib.SOLO_PAIRS_PER_INSTANCE * (l * 8 + OFFSETS[b]):][:plain.counts[l][b][0]] for b in range(B_IMGS)]).long(),
-                     plain.pair_inst[l])
+        assert G.same(torch.cat([pi[_lib.SOLO_PAIRS_PER_INSTANCE * (l * 8 + OFFSETS[b]):][:plain.counts[l][b][0]] for b in range(B_IMGS)]).long(),
+                      plain.pair_inst[l])
 
 
 def _cate_setup(dev, mode):
@@ -133,7 +123,7 @@ def test_cate_loss_guarded(dev, lead, mode):
 
     def call(maps, labels, num_ins, grads, loss, ws):
         rc = lib.bxi_solo_cate_loss_f32(pa(maps), grids, L, B_IMGS, C, labels, num_ins, s['gamma'], s['alpha'], s['loss_weight_cate'], pa(grads), loss,
-                                        ws, nbytes, _stream(dev))
+                                        ws, nbytes, G.stream(dev))
         assert rc == 0, _lib.STATUS.get(rc, rc)
 
     pg, pl, pw = [torch.empty_like(t) for t in preds], torch.empty(1, device=dev), torch.empty(nbytes // 4, device=dev)
@@ -147,9 +137,9 @@ def test_cate_loss_guarded(dev, lead, mode):
     G.check_bands(*gin, *gout, glab, gnum, gloss, gw)
     G.check_written(*gout, gloss, gw)
     G.check_unchanged(*gin, glab, gnum)
-    assert _same(gloss.t, pl) and bool(torch.isfinite(gloss.t).all()) and float(gloss.t) > 0
+    assert G.same(gloss.t, pl) and bool(torch.isfinite(gloss.t).all()) and float(gloss.t) > 0
     for got, want in zip(gout, pg):
-        assert _same(got.t, want) and bool(torch.isfinite(got.t).all())
+        assert G.same(got.t, want) and bool(torch.isfinite(got.t).all())
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
@@ -169,7 +159,7 @@ def test_cate_grad_rescale_guarded(dev, lead, in_place):
         gin = [G.embed(t, (lead + l) % 4, BAND) for l, t in enumerate(preds)]
         gout = [G.out(tuple(t.shape), torch.float32, dev, (lead + 2 + l) % 4, BAND) for l, t in enumerate(preds)]
     rc = _lib.load().bxi_solo_cate_grad_rescale_f32(grids, L, B_IMGS, C, _lib.ptr_array([t.ptr() for t in gin]), gup.ptr(),
-                                                    _lib.ptr_array([t.ptr() for t in gout]), _stream(dev))
+                                                    _lib.ptr_array([t.ptr() for t in gout]), G.stream(dev))
     assert rc == 0, _lib.STATUS.get(rc, rc)
     G.check_bands(gup, *gout)
     G.check_written(*gout)
@@ -178,4 +168,4 @@ def test_cate_grad_rescale_guarded(dev, lead, in_place):
         G.check_bands(*gin)
         G.check_unchanged(*gin)
     for got, src in zip(gout, preds):
-        assert _same(got.t, src * up[0])
+        assert G.same(got.t, src * up[0])

@@ -5,6 +5,7 @@ import torch
 
 from tests import guarded as G
 
+
 @pytest.mark.parametrize('dtype,lead', [(torch.float32, 0), (torch.float32, 3), (torch.float64, 1), (torch.int32, 1), (torch.int64, 1), (torch.uint8, 15)])
 def test_embed_places_the_view_and_the_poison(dtype, lead):
     t = (torch.arange(24) % 7).to(dtype).view(2, 3, 4)
@@ -66,3 +67,28 @@ def test_poisoned_empty_patches_and_restores():
         with G.poisoned_empty():
             1 / 0
     assert (torch.empty, torch.empty_like, torch.Tensor.new_empty) == real
+
+
+def test_same_ptr_ok_and_stream(monkeypatch):
+    for dtype, ibits in ((torch.float32, torch.int32), (torch.float64, torch.int64)):
+        quiet = torch.tensor([1.0, float('nan'), 0.0], dtype=dtype)
+        payload = quiet.clone()
+        payload.view(ibits)[1] += 1                                        # still a NaN, another payload
+        assert bool(torch.isnan(payload[1])) and G.same(quiet, quiet.clone()) and not G.same(quiet, payload)
+        assert not torch.equal(quiet, quiet.clone())                       # by value a NaN equals nothing: same() is the stricter and the usable one
+        zero, minus = torch.tensor([0.0], dtype=dtype), torch.tensor([-0.0], dtype=dtype)
+        assert torch.equal(zero, minus) and not G.same(zero, minus) and G.same(minus, minus.clone())
+    half = torch.tensor([0.0, 1.5], dtype=torch.float16)
+    assert G.same(half, half.clone()) and not G.same(half, -half) and not G.same(half, half.float()) and not G.same(half.float(), half.double())
+    wide = torch.arange(12, dtype=torch.float32).view(3, 4)
+    assert G.same(wide.t(), wide.t().contiguous()) and not G.same(wide, wide[:, :3])                 # views count by their elements
+    ints = torch.tensor([3, -1, 7])
+    assert G.same(ints, ints.clone()) and not G.same(ints, ints + 1) and G.same(ints > 0, torch.tensor([True, False, True]))
+    t = torch.zeros(5)
+    g = G.embed(t, 1, 64)
+    assert G.ptr(None) is None and G.ptr(t) == t.data_ptr() and G.ptr(g) == g.ptr() == g.backing.data_ptr() + 65 * 4
+    G.ok(0)
+    with pytest.raises(AssertionError, match='BXI_ERR_WORKSPACE'):
+        G.ok(-5)
+    monkeypatch.setattr(torch.cuda, 'current_stream', lambda dev: type('S', (), {'cuda_stream': (dev, 77)}))
+    assert G.stream('cuda:1') == ('cuda:1', 77)

@@ -2,13 +2,11 @@
 
 * tests/corr_ref.py, the restatement the GPU tests lean on, reproduces what the reference's own code computed (tests/golden/corr.npz,
   corr_planes_<case>.npz, make_golden_corr.py); with the reference present each case is regenerated live and compared;
-* include/boxinst/boxinst_hip_corr.h, the library's exports and _lib.CORR_SIGNATURES name the same entry points, none of them is in a
-  table of _lib.FAMILIES, and each is run by a named guarded test or is a ``_bytes`` query;
+* the limits of include/boxinst/boxinst_hip_corr.h are those of _lib, and INTEGRATION.md names the feature (the header against
+  _lib.CORR_SIGNATURES, the exports and the guarded tests: tests/test_abi_families.py);
 * the loss_corr block of every configs/discobox file is accepted (tests/golden/corr_cfg.json);
 * CPU tensors, wrong sizes and max_retrieval_objs > 8 fail before any launch."""
-import importlib
 import importlib.util
-import inspect
 import json
 import os
 import re
@@ -107,64 +105,19 @@ def test_fixture_is_what_the_reference_computes_now(name):
             assert json.load(fh) == json.loads(json.dumps(gen.config_blocks())), 'tests/golden/corr_cfg.json is not what the configs of the reference give'
 
 
-def _declarations(rel):
-    with open(os.path.join(ROOT, rel)) as fh:
-        code = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    decls = {}
-    for name in set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)):
-        found = re.search(r'\b' + name + r'\s*\(([^)]*)\)\s*;', code)
-        assert found, f'{name}: no declaration ending in ");" in {rel}'
-        decls[name] = [a for a in found.group(1).split(',') if a.strip() and a.strip() != 'void']
-    return decls, code
-
-
 def test_header_exports_and_signatures_agree():
+    """The family's own half; the header against the table and the exports is tests/test_abi_families.py[corr]."""
     from boxinstseg_amd import _lib
-    lib = _lib.load()
-    decls = {}
-    for rel in _lib.CORR_HEADERS:
-        d, code = _declarations(rel)
-        assert not set(d) & set(decls)
-        decls.update(d)
-    assert decls and sorted(decls) == sorted(_lib.CORR_SIGNATURES)
-    for n, (res, args) in _lib.CORR_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
-    for family, headers, table in _lib.FAMILIES:
-        assert not set(table) & set(_lib.CORR_SIGNATURES), family
-        for rel in headers:
-            assert not set(_declarations(rel)[0]) & set(_lib.CORR_SIGNATURES), rel
-    assert not any(table is _lib.CORR_SIGNATURES for _, _, table in _lib.FAMILIES)
+    with open(os.path.join(ROOT, 'include/boxinst/boxinst_hip_corr.h')) as fh:
+        code = fh.read()
     for macro, value in (('BXI_CORR_FEAT', _lib.CORR_FEAT), ('BXI_CORR_MASK', _lib.CORR_MASK), ('BXI_CORR_MAX_OBJS', _lib.CORR_MAX_OBJS),
                          ('BXI_CORR_MAX_QUEUE', _lib.CORR_MAX_QUEUE)):
         assert int(re.search(r'#define ' + macro + r' (\d+)', code).group(1)) == value, macro
     assert (R.FEAT, R.MASK) == (_lib.CORR_FEAT, _lib.CORR_MASK)
-    assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
     with open(os.path.join(ROOT, 'INTEGRATION.md')) as fh:
         integration = fh.read()
     for word in ('Level 3g', 'RoIAlign', '430 MB', 'num_gpu_bank', 'create_one', 'save_corr_img', 'perform_sinkhorn', 'corr_objects', 'bxi_corr_solve_f32'):
         assert word in integration, word
-
-
-def test_a_name_shared_with_a_family_fails_at_load(monkeypatch):
-    from boxinstseg_amd import _lib
-    monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'CORR_SIGNATURES', dict(_lib.CORR_SIGNATURES, bxi_mask_pack_u8=_lib.POST_SIGNATURES['bxi_mask_pack_u8']))
-    with pytest.raises(RuntimeError, match='bxi_mask_pack_u8 is in the signature tables of two ABI families: post and corr'):
-        _lib.load()
-
-
-def test_every_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    mod = importlib.import_module('tests.test_gpu_guarded_corr')
-    for entry, test in mod.GUARDED.items():
-        fn = getattr(mod, test, None)
-        assert callable(fn), f'{entry}: no test {test}'
-        assert entry in inspect.getsource(fn), entry
-    queries = {n for n in _lib.CORR_SIGNATURES if n.endswith('_bytes')}
-    assert queries == {'bxi_corr_workspace_bytes'} and not queries & set(mod.GUARDED)
-    assert set(mod.GUARDED) | queries == set(_lib.CORR_SIGNATURES)
 
 
 def test_reference_corr_blocks_are_accepted():

@@ -3,12 +3,11 @@
 * statement (i) of tests/masked_attn_ref.py (torch's nn.MultiheadAttention) and its per-head restatement (ii) agree within 1e-12 in fp64, with
   identity and with random projections, with a 3-D, a 2-D and no mask;
 * the fixture is what the restated statements of box2mask_head.py give now; its planted rows are what they were planted for;
-* include/boxinst/boxinst_hip_attn.h, the library's exports and _lib.ATTN_SIGNATURES name the same entry points with the same argument counts,
-  none of them in another table, and each is run by a named guarded test or is a ``_bytes`` query;
+* the limits of include/boxinst/boxinst_hip_attn.h are those of _lib, and INTEGRATION.md names the feature (the header against
+  _lib.ATTN_SIGNATURES, the exports and the guarded tests: tests/test_abi_families.py);
 * the attn_cfgs block of the transformer decoder of the reference's Box2Mask configs builds the module; its state-dict keys and shapes are
   those of nn.MultiheadAttention(256, 8) under ``attn.``;
 * unsupported arguments fail before any launch."""
-import importlib
 import inspect
 import json
 import os
@@ -74,68 +73,20 @@ def test_pack_bits_by_hand():
     assert b.tolist() == [[1 - 2 ** 31, 1], [0, 4]] and torch.equal(R.unpack_bits(b, 35), m)
 
 
-def _declarations(rel):
-    with open(os.path.join(ROOT, rel)) as fh:
-        code = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    decls = {}
-    for name in set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)):
-        found = re.search(r'\b' + name + r'\s*\(([^)]*)\)\s*;', code)
-        assert found, f'{name}: no declaration ending in ");" in {rel}'
-        decls[name] = [a for a in found.group(1).split(',') if a.strip() and a.strip() != 'void']
-    return decls, code
-
-
 def test_header_exports_and_signatures_agree():
+    """The family's own half; the header against the table and the exports is tests/test_abi_families.py[attn]."""
     from boxinstseg_amd import _lib
-    lib = _lib.load()
-    decls = {}
-    for rel in _lib.ATTN_HEADERS:
-        d, code = _declarations(rel)
-        decls.update(d)
-    assert decls and sorted(decls) == sorted(_lib.ATTN_SIGNATURES) and len(decls) == 6
-    for n, (res, args) in _lib.ATTN_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
-    others = [('corr', _lib.CORR_HEADERS, _lib.CORR_SIGNATURES), ('roi', _lib.ROI_HEADERS, _lib.ROI_SIGNATURES),
-              ('msda', _lib.MSDA_HEADERS, _lib.MSDA_SIGNATURES), ('seg', _lib.SEG_HEADERS, _lib.SEG_SIGNATURES),
-              ('dconv', _lib.DCONV_HEADERS, _lib.DCONV_SIGNATURES)] + list(_lib.FAMILIES)
-    for family, headers, table in others:
-        assert not set(table) & set(_lib.ATTN_SIGNATURES), family
-        assert table is not _lib.ATTN_SIGNATURES
-        for rel in headers:
-            assert not set(_declarations(rel)[0]) & set(_lib.ATTN_SIGNATURES), rel
+    with open(os.path.join(ROOT, 'include/boxinst/boxinst_hip_attn.h')) as fh:
+        code = fh.read()
+    assert len(_lib.ATTN_SIGNATURES) == 6
     for macro, value in (('BXI_ATTN_SPAN', _lib.ATTN_SPAN), ('BXI_ATTN_MAX_Q', _lib.ATTN_MAX_Q), ('BXI_ATTN_MAX_S', _lib.ATTN_MAX_S),
                          ('BXI_ATTN_MAX_HEADS', _lib.ATTN_MAX_HEADS)):
         assert int(re.search(r'#define ' + macro + r' (\d+)', code).group(1)) == value, macro
-    assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
-    assert 'attn' not in [f[0] for f in _lib.FAMILIES]
     with open(os.path.join(ROOT, 'INTEGRATION.md')) as fh:
         integration = fh.read()
     for word in ('Level 3l', 'box2mask_attn_mask', 'masked_attention', 'v < 0', 'not repeated', 'unpinned', 'build_attention', 'key_padding_mask'):
         assert word in integration, word
-    with open(os.path.join(ROOT, 'include/boxinst/boxinst_hip_attn.h')) as fh:
-        assert 'v < 0' in fh.read()
-
-
-def test_a_name_shared_with_another_table_fails_at_load(monkeypatch):
-    from boxinstseg_amd import _lib
-    monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'ATTN_SIGNATURES', dict(_lib.ATTN_SIGNATURES, bxi_msda_forward_f32=_lib.MSDA_SIGNATURES['bxi_msda_forward_f32']))
-    with pytest.raises(RuntimeError, match='bxi_msda_forward_f32 is in the signature tables of two ABI families: msda and attn'):
-        _lib.load()
-
-
-def test_every_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    mod = importlib.import_module('tests.test_gpu_guarded_attn')
-    for entry, test in mod.GUARDED.items():
-        fn = getattr(mod, test, None)
-        assert callable(fn), f'{entry}: no test {test}'
-        assert entry in inspect.getsource(fn), entry
-    queries = {n for n in _lib.ATTN_SIGNATURES if n.endswith('_bytes')}
-    assert queries == {'bxi_masked_attn_forward_workspace_bytes', 'bxi_masked_attn_backward_workspace_bytes'} and not queries & set(mod.GUARDED)
-    assert set(mod.GUARDED) | queries == set(_lib.ATTN_SIGNATURES)
+    assert 'v < 0' in code
 
 
 def test_reference_config_block_builds_the_module():
@@ -205,6 +156,15 @@ def test_unsupported_arguments_fail_before_any_launch():
         B.pack_attn_mask(torch.zeros(5, 7, dtype=torch.bool), 2)
     with pytest.raises(NotImplementedError, match='bool'):
         B.pack_attn_mask(torch.zeros(5, 7), 2)
+
+
+def test_unsupported_status_names_the_header():
+    from boxinstseg_amd import _lib, masked_attn
+    masked_attn._status('bxi_masked_attn_forward_f32', 0)
+    with pytest.raises(NotImplementedError, match='^bxi_masked_attn_forward_f32: outside the support set of include/boxinst/boxinst_hip_attn.h$'):
+        masked_attn._status('bxi_masked_attn_forward_f32', _lib.BXI_ERR_UNSUPPORTED)
+    with pytest.raises(_lib.BoxInstHipError, match='^bxi_masked_attn_forward_f32: BXI_ERR_BAD_SHAPE -- '):
+        masked_attn._status('bxi_masked_attn_forward_f32', -2)
 
 
 def test_abi_validation_without_device():

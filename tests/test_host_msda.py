@@ -3,8 +3,8 @@
 * the two restatements of tests/msda_ref.py -- mmcv's op never ran here, its arithmetic is unpinned -- agree forward and in every gradient,
   and obey rules checked by hand;
 * the fixture is what the restatement computes now, its inputs keep off the grid, its tolerances are of the size of fp32 rounding;
-* include/boxinst/boxinst_hip_msda.h, the library's exports and _lib.MSDA_SIGNATURES name the same entry points, none of them in another table,
-  and each is run by a named guarded test or is a ``_bytes`` query;
+* the limits of include/boxinst/boxinst_hip_msda.h are those of _lib, and INTEGRATION.md names the feature (the header against
+  _lib.MSDA_SIGNATURES, the exports and the guarded tests: tests/test_abi_families.py);
 * the attn_cfgs block of the reference's Box2Mask configs builds the module; its state-dict keys and init_weights are the restated module's;
 * bad arguments, CPU tensors, half precision and shapes outside the support set fail before any launch;
 * the premise of tests/test_gpu_msda_fixed_point.py holds for the restatement alone: on the dyadic cases fp32 and fp64 give the same bits;
@@ -199,64 +199,19 @@ def test_reference_config_block_builds_the_module():
         assert name in B.__all__ and name in B.__doc__
 
 
-def _declarations(rel):
-    with open(os.path.join(ROOT, rel)) as fh:
-        code = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    decls = {}
-    for name in set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)):
-        found = re.search(r'\b' + name + r'\s*\(([^)]*)\)\s*;', code)
-        assert found, f'{name}: no declaration ending in ");" in {rel}'
-        decls[name] = [a for a in found.group(1).split(',') if a.strip() and a.strip() != 'void']
-    return decls, code
-
-
 def test_header_exports_and_signatures_agree():
+    """The family's own half; the header against the table and the exports is tests/test_abi_families.py[msda]."""
     from boxinstseg_amd import _lib
-    lib = _lib.load()
-    decls = {}
-    for rel in _lib.MSDA_HEADERS:
-        d, code = _declarations(rel)
-        decls.update(d)
-    assert decls and sorted(decls) == sorted(_lib.MSDA_SIGNATURES)
-    for n, (res, args) in _lib.MSDA_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
-    others = [('corr', _lib.CORR_HEADERS, _lib.CORR_SIGNATURES), ('roi', _lib.ROI_HEADERS, _lib.ROI_SIGNATURES)] + list(_lib.FAMILIES)
-    for family, headers, table in others:
-        assert not set(table) & set(_lib.MSDA_SIGNATURES), family
-        assert table is not _lib.MSDA_SIGNATURES
-        for rel in headers:
-            assert not set(_declarations(rel)[0]) & set(_lib.MSDA_SIGNATURES), rel
+    with open(os.path.join(ROOT, 'include/boxinst/boxinst_hip_msda.h')) as fh:
+        code = fh.read()
     for macro, value in (('BXI_MSDA_MAX_LEVELS', _lib.MSDA_MAX_LEVELS), ('BXI_MSDA_MAX_POINTS', _lib.MSDA_MAX_POINTS),
                          ('BXI_MSDA_MIN_HEAD_DIM', _lib.MSDA_MIN_HEAD_DIM), ('BXI_MSDA_MAX_HEAD_DIM', _lib.MSDA_MAX_HEAD_DIM),
                          ('BXI_MSDA_FUSED', _lib.MSDA_FUSED), ('BXI_MSDA_MAX_CELL_SAMPLES', _lib.MSDA_MAX_CELL_SAMPLES)):
         assert int(re.search(r'#define ' + macro + r' (\d+)', code).group(1)) == value, macro
-    assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
     with open(os.path.join(ROOT, 'INTEGRATION.md')) as fh:
         integration = fh.read()
     for word in ('Level 3i', 'multi_scale_deformable_attn_fused', 'unpinned', 'h = -1', 'grid_sample', 'build_attention', 'fixed point'):
         assert word in integration, word
-
-
-def test_a_name_shared_with_another_table_fails_at_load(monkeypatch):
-    from boxinstseg_amd import _lib
-    monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'MSDA_SIGNATURES', dict(_lib.MSDA_SIGNATURES, bxi_roi_align_forward_f32=_lib.ROI_SIGNATURES['bxi_roi_align_forward_f32']))
-    with pytest.raises(RuntimeError, match='bxi_roi_align_forward_f32 is in the signature tables of two ABI families: roi and msda'):
-        _lib.load()
-
-
-def test_every_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    mod = importlib.import_module('tests.test_gpu_guarded_msda')
-    for entry, test in mod.GUARDED.items():
-        fn = getattr(mod, test, None)
-        assert callable(fn), f'{entry}: no test {test}'
-        assert entry in inspect.getsource(fn), entry
-    queries = {n for n in _lib.MSDA_SIGNATURES if n.endswith('_bytes')}
-    assert queries == {'bxi_msda_backward_workspace_bytes'} and not queries & set(mod.GUARDED)
-    assert set(mod.GUARDED) | queries == set(_lib.MSDA_SIGNATURES)
 
 
 def test_cpu_tensors_and_bad_arguments_fail_loudly():
@@ -295,6 +250,15 @@ def test_cpu_tensors_and_bad_arguments_fail_loudly():
     assert msda._levels([(2, 3)], [0], 6, 'cpu')[2] == 1
     with pytest.raises(NotImplementedError, match='power of two'):
         msda._unsupported(2, 12, 1, 1)
+
+
+def test_unsupported_status_names_the_header():
+    from boxinstseg_amd import _lib, msda
+    msda._status('bxi_msda_forward_f32', 0)
+    with pytest.raises(NotImplementedError, match='^bxi_msda_forward_f32: outside the support set of include/boxinst/boxinst_hip_msda.h$'):
+        msda._status('bxi_msda_forward_f32', _lib.BXI_ERR_UNSUPPORTED)
+    with pytest.raises(_lib.BoxInstHipError, match='^bxi_msda_forward_f32: BXI_ERR_BAD_SHAPE -- '):
+        msda._status('bxi_msda_forward_f32', -2)
 
 
 def test_abi_validation_without_device():

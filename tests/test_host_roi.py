@@ -4,12 +4,11 @@
   make_golden_roi.py); with the reference present the case is regenerated live and compared;
 * the restated RoIAlign -- mmcv's op never ran here, its arithmetic is unpinned -- equals a second statement built from F.grid_sample, and
   obeys rules checked by hand;
-* include/boxinst/boxinst_hip_roi.h, the library's exports and _lib.ROI_SIGNATURES name the same entry points, none of them is in a table
-  of _lib.FAMILIES or in CORR_SIGNATURES, and each is run by a named guarded test or is a ``_bytes`` query;
+* the limits of include/boxinst/boxinst_hip_roi.h are those of _lib, and INTEGRATION.md names the feature (the header against
+  _lib.ROI_SIGNATURES, the exports and the guarded tests: tests/test_abi_families.py);
 * bad arguments, CPU tensors and pool_mode='max' fail before any launch."""
 import importlib
 import importlib.util
-import inspect
 import json
 import os
 import re
@@ -133,67 +132,19 @@ def test_restatement_rules_by_hand():
     assert float(R.relu_and_l2_norm_feat(f)[0, 1]) == pytest.approx(2.0 / ((4.0 + 1e-6) ** 0.5 + 1e-6), rel=1e-14)
 
 
-def _declarations(rel):
-    with open(os.path.join(ROOT, rel)) as fh:
-        code = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    decls = {}
-    for name in set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)):
-        found = re.search(r'\b' + name + r'\s*\(([^)]*)\)\s*;', code)
-        assert found, f'{name}: no declaration ending in ");" in {rel}'
-        decls[name] = [a for a in found.group(1).split(',') if a.strip() and a.strip() != 'void']
-    return decls, code
-
-
 def test_header_exports_and_signatures_agree():
+    """The family's own half; the header against the table and the exports is tests/test_abi_families.py[roi]."""
     from boxinstseg_amd import _lib
-    lib = _lib.load()
-    decls = {}
-    for rel in _lib.ROI_HEADERS:
-        d, code = _declarations(rel)
-        assert not set(d) & set(decls)
-        decls.update(d)
-    assert decls and sorted(decls) == sorted(_lib.ROI_SIGNATURES)
-    for n, (res, args) in _lib.ROI_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
-    assert not set(_lib.ROI_SIGNATURES) & set(_lib.CORR_SIGNATURES)
-    for rel in _lib.CORR_HEADERS:
-        assert not set(_declarations(rel)[0]) & set(_lib.ROI_SIGNATURES), rel
-    for family, headers, table in _lib.FAMILIES:
-        assert not set(table) & set(_lib.ROI_SIGNATURES), family
-        for rel in headers:
-            assert not set(_declarations(rel)[0]) & set(_lib.ROI_SIGNATURES), rel
-    assert not any(table is _lib.ROI_SIGNATURES for _, _, table in _lib.FAMILIES)
+    with open(os.path.join(ROOT, 'include/boxinst/boxinst_hip_roi.h')) as fh:
+        code = fh.read()
     for macro, value in (('BXI_ROI_MAX_POOL', _lib.ROI_MAX_POOL), ('BXI_ROI_MAX_SAMPLING', _lib.ROI_MAX_SAMPLING), ('BXI_ROI_MAX_SIDE', _lib.ROI_MAX_SIDE),
                          ('BXI_ROI_FUSED_MAX_C', _lib.ROI_FUSED_MAX_C), ('BXI_ROI_FEAT', _lib.ROI_FEAT), ('BXI_ROI_SIGMOID', _lib.ROI_SIGMOID)):
         assert int(re.search(r'#define ' + macro + r' (\d+)', code).group(1)) == value, macro
     assert (R.FEAT, R.MASK) == (_lib.ROI_FEAT, _lib.CORR_MASK) == (_lib.CORR_FEAT, 28)
-    assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
     with open(os.path.join(ROOT, 'INTEGRATION.md')) as fh:
         integration = fh.read()
     for word in ('Level 3h', 'corr_level', 'unpinned', 'own_labels', "pool_mode='max'", 'img_roi_align', 'bxi_roi_feat_norm_forward_f32', 'BXI_ERR_UNSUPPORTED'):
         assert word in integration, word
-
-
-def test_a_name_shared_with_another_table_fails_at_load(monkeypatch):
-    from boxinstseg_amd import _lib
-    monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'ROI_SIGNATURES', dict(_lib.ROI_SIGNATURES, bxi_corr_superres_f32=_lib.CORR_SIGNATURES['bxi_corr_superres_f32']))
-    with pytest.raises(RuntimeError, match='bxi_corr_superres_f32 is in the signature tables of two ABI families: corr and roi'):
-        _lib.load()
-
-
-def test_every_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    mod = importlib.import_module('tests.test_gpu_guarded_roi')
-    for entry, test in mod.GUARDED.items():
-        fn = getattr(mod, test, None)
-        assert callable(fn), f'{entry}: no test {test}'
-        assert entry in inspect.getsource(fn), entry
-    queries = {n for n in _lib.ROI_SIGNATURES if n.endswith('_bytes')}
-    assert queries == {'bxi_roi_feat_norm_workspace_bytes'} and not queries & set(mod.GUARDED)
-    assert set(mod.GUARDED) | queries == set(_lib.ROI_SIGNATURES)
 
 
 def test_exports_and_pool_mode_max():

@@ -3,12 +3,10 @@
 * bxi_seg_paste_u8 validates its arguments before anything touches a device: every call below fails (or is a no-op) with pointers nothing
   dereferences;
 * the workspace size is one 16-byte record per mask, output row and chunk of 1024 columns, monotone in n, 0 for what the entry point refuses;
-* include/boxinst/boxinst_hip_seg.h, the library's exports and _lib.SEG_SIGNATURES name the same entry points, none of them in another
-  table, and each is run by a named guarded test or is a ``_bytes`` query;
+* _lib.SEG_SIGNATURES holds the two entry points and the build lists the sources (include/boxinst/boxinst_hip_seg.h against the table,
+  the exports and the guarded tests: tests/test_abi_families.py);
 * the documents name the feature; CPU tensors raise; the two restatements of tests/seg_paste_ref.py agree with torch's own fp32 composition
   under the tie rule and with a count by hand."""
-import importlib
-import inspect
 import os
 import re
 
@@ -26,17 +24,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.fixture(scope='module', autouse=True)
 def _built(built):
     return built
-
-
-def _declarations(rel):
-    with open(os.path.join(ROOT, rel)) as fh:
-        code = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    decls = {}
-    for name in set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)):
-        found = re.search(r'\b' + name + r'\s*\(([^)]*)\)\s*;', code)
-        assert found, f'{name}: no declaration ending in ");" in {rel}'
-        decls[name] = [a for a in found.group(1).split(',') if a.strip() and a.strip() != 'void']
-    return decls
 
 
 def test_abi_validation_without_device():
@@ -81,44 +68,10 @@ def test_workspace_size():
 
 
 def test_header_exports_and_signatures_agree():
-    from boxinstseg_amd import _lib
-    lib = _lib.load()
-    decls = {}
-    for rel in _lib.SEG_HEADERS:
-        decls.update(_declarations(rel))
-    assert decls and sorted(decls) == sorted(_lib.SEG_SIGNATURES) == ['bxi_seg_paste_u8', 'bxi_seg_paste_workspace_bytes']
-    for n, (res, args) in _lib.SEG_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
-    others = [('corr', _lib.CORR_HEADERS, _lib.CORR_SIGNATURES), ('roi', _lib.ROI_HEADERS, _lib.ROI_SIGNATURES),
-              ('msda', _lib.MSDA_HEADERS, _lib.MSDA_SIGNATURES)] + list(_lib.FAMILIES)
-    for family, headers, table in others:
-        assert family != 'seg' and not set(table) & set(_lib.SEG_SIGNATURES), family
-        for rel in headers:
-            assert not set(_declarations(rel)) & set(_lib.SEG_SIGNATURES), rel
-    assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
-    from boxinstseg_amd import build
+    """The family's own half; the header against the table and the exports is tests/test_abi_families.py[seg]."""
+    from boxinstseg_amd import _lib, build
+    assert sorted(_lib.SEG_SIGNATURES) == ['bxi_seg_paste_u8', 'bxi_seg_paste_workspace_bytes']
     assert 'seg_paste.hip' in build.SOURCES and 'paste_device.hpp' in build.HEADERS
-
-
-def test_a_name_shared_with_another_table_fails_at_load(monkeypatch):
-    from boxinstseg_amd import _lib
-    monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'SEG_SIGNATURES', dict(_lib.SEG_SIGNATURES, bxi_mask_pack_u8=_lib.POST_SIGNATURES['bxi_mask_pack_u8']))
-    with pytest.raises(RuntimeError, match='bxi_mask_pack_u8 is in the signature tables of two ABI families: post and seg'):
-        _lib.load()
-
-
-def test_every_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    mod = importlib.import_module('tests.test_gpu_guarded_seg')
-    for entry, test in mod.GUARDED.items():
-        fn = getattr(mod, test, None)
-        assert callable(fn), f'{entry}: no test {test}'
-        assert entry in inspect.getsource(mod._call) and '_call(' in inspect.getsource(fn), entry
-    queries = {n for n in _lib.SEG_SIGNATURES if n.endswith('_bytes')}
-    assert queries == {'bxi_seg_paste_workspace_bytes'} and set(mod.GUARDED) | queries == set(_lib.SEG_SIGNATURES)
 
 
 def test_documents_name_the_feature():

@@ -3,12 +3,11 @@
 * bxi_solo_dconv_forward_f32 / _backward_f32 validate their arguments before anything touches a device: every call below fails (or is a
   no-op) with pointers nothing dereferences -- every limit of the header, the NULL combinations, the workspace NULL / short / misaligned;
 * the workspace size is monotone in N and in the tiles and 0 for what the entry point refuses;
-* include/boxinst/boxinst_hip_dconv.h, the library's exports and _lib.DCONV_SIGNATURES name the same entry points, none of them in another
-  table; a shared name fails at load; each entry point is run by a named guarded test or is a ``_bytes`` query;
+* the constants of include/boxinst/boxinst_hip_dconv.h are those of _lib, _lib.DCONV_SIGNATURES holds the four entry points and the build
+  lists the sources (the header against the table, the exports and the guarded tests: tests/test_abi_families.py);
 * CPU tensors raise; the documents name the feature;
 * tests/solo_conv_ref.py reproduces tests/golden/solo_conv.npz (which its generator ties to the reference's statements) and a case counted
   by hand."""
-import importlib
 import inspect
 import os
 import re
@@ -27,17 +26,6 @@ X = 0x1000                                                                    # 
 @pytest.fixture(scope='module', autouse=True)
 def _built(built):
     return built
-
-
-def _declarations(rel):
-    with open(os.path.join(ROOT, rel)) as fh:
-        code = re.sub(r'/\*.*?\*/', '', fh.read(), flags=re.S)
-    decls = {}
-    for name in set(re.findall(r'\b(bxi_[a-z0-9_]+)\s*\(', code)):
-        found = re.search(r'\b' + name + r'\s*\(([^)]*)\)\s*;', code)
-        assert found, f'{name}: no declaration ending in ");" in {rel}'
-        decls[name] = [a for a in found.group(1).split(',') if a.strip() and a.strip() != 'void']
-    return decls
 
 
 def _callers():
@@ -141,25 +129,11 @@ def test_workspace_size():
 
 
 def test_header_exports_and_signatures_agree():
+    """The family's own half; the header against the table and the exports is tests/test_abi_families.py[dconv]."""
     from boxinstseg_amd import _lib
-    lib = _lib.load()
-    decls = {}
-    for rel in _lib.DCONV_HEADERS:
-        decls.update(_declarations(rel))
-    assert decls and sorted(decls) == sorted(_lib.DCONV_SIGNATURES) == [
+    assert sorted(_lib.DCONV_SIGNATURES) == [
         'bxi_solo_dconv_backward_f32', 'bxi_solo_dconv_backward_workspace_bytes', 'bxi_solo_dconv_forward_f32', 'bxi_solo_dconv_forward_workspace_bytes']
-    for n, (res, args) in _lib.DCONV_SIGNATURES.items():
-        fn = getattr(lib, n)
-        assert fn.restype == res and list(fn.argtypes) == list(args), n
-        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
-    others = [('corr', _lib.CORR_HEADERS, _lib.CORR_SIGNATURES), ('roi', _lib.ROI_HEADERS, _lib.ROI_SIGNATURES),
-              ('msda', _lib.MSDA_HEADERS, _lib.MSDA_SIGNATURES), ('seg', _lib.SEG_HEADERS, _lib.SEG_SIGNATURES)] + list(_lib.FAMILIES)
-    for family, headers, table in others:
-        assert family != 'dconv' and not set(table) & set(_lib.DCONV_SIGNATURES), family
-        for rel in headers:
-            assert not set(_declarations(rel)) & set(_lib.DCONV_SIGNATURES), rel
-    assert lib.bxi_abi_version() == _lib.BXI_ABI_VERSION == 7                # additive: the version stays
-    with open(os.path.join(ROOT, _lib.DCONV_HEADERS[0])) as fh:
+    with open(os.path.join(ROOT, 'include/boxinst/boxinst_hip_dconv.h')) as fh:
         text = fh.read()
     for name in ('DCONV_MAPS', 'DCONV_ROWS', 'DCONV_NONE', 'DCONV_SIGMOID', 'DCONV_MAX_LEVELS', 'DCONV_MAX_E', 'DCONV_TILE', 'DCONV_STATUS_BAD_CELL'):
         assert re.search(r'#define BXI_' + name + r' (\d+)', text).group(1) == str(getattr(_lib, name)), name
@@ -167,25 +141,6 @@ def test_header_exports_and_signatures_agree():
     from boxinstseg_amd import build
     assert 'solo_dconv.hip' in build.SOURCES and any(h.endswith('boxinst_hip_dconv.h') for h in build.HEADERS)
     assert all(os.path.exists(os.path.join(build.CSRC, h)) for h in build.HEADERS)
-
-
-def test_a_name_shared_with_another_table_fails_at_load(monkeypatch):
-    from boxinstseg_amd import _lib
-    monkeypatch.setattr(_lib, '_lib', None)
-    monkeypatch.setattr(_lib, 'DCONV_SIGNATURES', dict(_lib.DCONV_SIGNATURES, bxi_seg_paste_u8=_lib.SEG_SIGNATURES['bxi_seg_paste_u8']))
-    with pytest.raises(RuntimeError, match='bxi_seg_paste_u8 is in the signature tables of two ABI families: seg and dconv'):
-        _lib.load()
-
-
-def test_every_entry_point_is_guarded_or_a_size_query():
-    from boxinstseg_amd import _lib
-    mod = importlib.import_module('tests.test_gpu_guarded_solo_conv')
-    for entry, test in mod.GUARDED.items():
-        fn = getattr(mod, test, None)
-        assert callable(fn), f'{entry}: no test {test}'
-        assert 'lib.' + entry + '(' in inspect.getsource(mod._call) and '_call(' in inspect.getsource(fn), entry
-    queries = {n for n in _lib.DCONV_SIGNATURES if n.endswith('_bytes')}
-    assert queries == {'bxi_solo_dconv_backward_workspace_bytes', 'bxi_solo_dconv_forward_workspace_bytes'} and set(mod.GUARDED) | queries == set(_lib.DCONV_SIGNATURES)
 
 
 def test_documents_name_the_feature():
