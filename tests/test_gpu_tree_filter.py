@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import tree_filter_oracle as tfo
+from tests import tree_filter_ref as R
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
@@ -224,7 +225,173 @@ def test_tree_filter_module_end_to_end(built, dev):
             assert np.abs(got - want).max() <= 3e-5 * max(np.abs(want).max(), 1.0)       # independent of the BFS order used
             gf = tfo.refine_backward_feature(gout[b, 2 * gidx:2 * gidx + 2].reshape(2, V).astype(np.float64), w, si, sp, sc, saved)
             assert np.abs(fd.grad[b, 2 * gidx:2 * gidx + 2].cpu().numpy().reshape(2, V) - gf).max() <= 3e-5 * max(np.abs(gf).max(), 1.0)
-    assert ed.grad is not None and torch.isfinite(ed.grad).all() and float(ed.grad.abs().sum()) > 0
+    # the embedding gradient: bxi_tree_refine_backward_weight_f32 + the torch glue of build_edge_weight, per image and group
+    info = {}
+    _, _, want_e = R.module_reference(feat, emb, tree.cpu().numpy(), 2, False, tf2.sigma, gout, info)
+    assert ed.grad is not None and ed.grad.shape == ed.shape
+    _check_embedding_grad('module 16x20, 2 groups', ed.grad.cpu().numpy(), want_e, info['gw_absmax'])
+
+
+# d loss / d embedding = sum over the (at most 4) tree edges at a grid vertex of d loss / d w * d w / d e, and per channel
+# |d w / d e| = 2 |de| exp(-de^2) <= sqrt(2 / e) = 0.858 for w = exp(-d); the weight gradient itself is held to 1e-4 * max(|gw|max, 1)
+# (test_refine_forward_backward_vs_oracle).  gw: the fp64 weight gradient of that image and group.
+EMB_GRAD_TOL = 4 * 0.858 * 1e-4
+
+
+def _check_embedding_grad(what, got, want, gw_absmax):
+    B, G = gw_absmax.shape
+    eg = want.shape[1] // G
+    assert np.isfinite(got).all()
+    ok = True
+    for b in range(B):
+        for g in range(G):
+            es = slice(g * eg, (g + 1) * eg)
+            tol = EMB_GRAD_TOL * max(float(gw_absmax[b, g]), 1.0)
+            err = float(np.abs(got[b, es] - want[b, es]).max())
+            print(f'{what}: image {b} group {g}: embedding gradient max error {err:.3g} = {err / tol:.3g} of the tolerance {tol:.3g} '
+                  f'(max |want| {np.abs(want[b, es]).max():.3g}, max |gw| {gw_absmax[b, g]:.3g})')
+            ok = ok and err <= tol
+    assert ok, what
+
+
+def test_tree_filter_module_box2mask_call_shape(built, dev):
+    """Box2Mask's second filter (box2mask_head.py:284-287, 321-322): one mask channel per instance, the three instances of an image on
+    that image's repeated tree and repeated 3-channel embedding, groups = 1, low_tree=False -- forward and both gradients"""
+    from boxinstseg_amd import MinimumSpanningTree, TreeFilter2D
+    rng = np.random.default_rng(12)
+    N, H, W = 3, 12, 17
+    lst = (rng.standard_normal((1, 3, H, W)) * 0.4).astype(np.float32)
+    tree = MinimumSpanningTree(TreeFilter2D.norm2_distance)(torch.from_numpy(lst).to(dev)).repeat(N, 1, 1)
+    emb = np.ascontiguousarray(np.repeat(lst, N, 0))
+    feat = rng.uniform(0, 1, (N, 1, H, W)).astype(np.float32)
+    gout = rng.standard_normal((N, 1, H, W)).astype(np.float32)
+    fd = torch.from_numpy(feat).to(dev).requires_grad_(True)
+    ed = torch.from_numpy(emb).to(dev).requires_grad_(True)
+    tf = TreeFilter2D()
+    out = tf(fd, ed, tree, low_tree=False)
+    out.backward(torch.from_numpy(gout).to(dev))
+    info = {}
+    want, want_f, want_e = R.module_reference(feat, emb, tree.cpu().numpy(), 1, False, tf.sigma, gout, info)
+    assert np.abs(out.detach().cpu().numpy() - want).max() <= 3e-5 * max(np.abs(want).max(), 1.0)
+    assert np.abs(fd.grad.cpu().numpy() - want_f).max() <= 3e-5 * max(np.abs(want_f).max(), 1.0)
+    _check_embedding_grad('module 12x17, 3 instances on one tree', ed.grad.cpu().numpy(), want_e, info['gw_absmax'])
+
+
+def _default_module_case(dev, B, H, W, seed):
+    """TreeFilter2D()(feat, emb, tree) as Box2Mask's first filter calls it (box2mask_head.py:319-320): low_tree=True, sigma 0.02, one mask
+    channel, the tree of the image that is also the embedding, and the weights such an image gives (R.image_like_embedding): exactly 1,
+    exactly 0 after underflow, and everything between."""
+    from boxinstseg_amd import MinimumSpanningTree, TreeFilter2D
+    rng = np.random.default_rng(seed)
+    V = H * W
+    emb = R.image_like_embedding(B, 3, H, W, rng)
+    feat = rng.uniform(0, 1, (B, 1, H, W)).astype(np.float32)
+    gout = rng.standard_normal((B, 1, H, W)).astype(np.float32)
+    tree = MinimumSpanningTree(TreeFilter2D.norm2_distance)(torch.from_numpy(emb).to(dev))
+    tf = TreeFilter2D()
+    assert tf.groups == 1 and tf.sigma == 0.02
+    t = tree.cpu().numpy()
+    for b in range(B):                                  # the weights are the real ones: an exact 1 and an exact 0 both occur in fp32
+        si, sp, _ = tfo.bfs_order(t[b], V)
+        w32 = tfo.edge_weights(emb[b].reshape(3, V), si, sp, True, tf.sigma).astype(np.float32)[1:]
+        assert (w32 == 1).any() and (w32 == 0).any() and ((w32 > 0) & (w32 < 1)).any()
+    fd = torch.from_numpy(feat).to(dev).requires_grad_(True)
+    ed = torch.from_numpy(emb).to(dev).requires_grad_(True)
+    out = tf(fd, ed, tree)
+    out.backward(torch.from_numpy(gout).to(dev))
+    want, want_f, want_e = R.module_reference(feat, emb, t, 1, True, tf.sigma, gout)
+    assert want_e is None and np.isfinite(want).all() and np.isfinite(want_f).all()
+    got, got_f = out.detach().cpu().numpy(), fd.grad.cpu().numpy()
+    assert np.isfinite(got).all() and np.isfinite(got_f).all()
+    assert np.abs(got - want).max() <= 3e-5 * max(np.abs(want).max(), 1.0)
+    assert np.abs(got_f - want_f).max() <= 3e-5 * max(np.abs(want_f).max(), 1.0)
+    assert ed.requires_grad and ed.grad is None         # functions/refine.py:32-33: no gradient to the weights of the low-level tree
+
+
+def test_tree_filter_module_default_low_tree(built, dev):
+    _default_module_case(dev, 2, 12, 17, 21)
+
+
+# ---- edge weights of exactly 0, exactly 1 and fp32 subnormals ------------------------------------------------------------------------
+_REGIME_REF = {}        # (tree, regime) -> orders and fp64 results: computed once, shared by the forms of the large kernels
+
+
+def _regime_tree(dev, name):
+    from boxinstseg_amd import mst
+    if name.startswith('strip'):
+        V = int(name[5:])
+        t = np.stack([np.arange(V - 1), np.arange(1, V)], 1).astype(np.int32)
+        return torch.from_numpy(t)[None].to(dev), V
+    H, W = (int(v) for v in name[3:].split('x'))
+    V = H * W
+    idx = tfo.grid_edges(H, W)
+    fm = np.random.default_rng(V).standard_normal((3, H, W)).astype(np.float32)
+    return mst(torch.from_numpy(idx)[None].to(dev), torch.from_numpy(tfo.grid_weights(fm))[None].to(dev), V), V
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def _run_weight_regime(dev, tree_name, regime):
+    """refine() (low_tree=False: both gradients) on R.regime_inputs: finite and within the usual bounds of the fp64 oracle in every
+    regime; bit for bit where every intermediate is an integer below 2^24 or an exact multiple of 1 / V (V a power of two) -- 'zeros'
+    (the filter is the identity), 'ones' (the mean of the whole tree), 'cut' (the mean of each component of the edges with w == 1;
+    the one rounding is the final IEEE division).
+
+    What the exact regimes cannot see: with w in {0, 1}, 1 - w*w = 1 - w, and w*w = w, so a kernel that confuses the two passes
+    'ones', 'zeros' and 'cut'; 'mixed' (0.5 and the values near the underflow threshold) and the oracle tests on random weights catch it."""
+    from boxinstseg_amd import bfs, refine
+    tree, V = _regime_tree(dev, tree_name)
+    B, C = 2, 2
+    assert V & (V - 1) == 0
+    x, g, w = R.regime_inputs(regime, V, B, C)
+    si, sp, sc = bfs(tree.repeat(B, 1, 1), 4)
+    sin, spn, scn = si.cpu().numpy(), sp.cpu().numpy(), sc.cpu().numpy()
+    assert np.array_equal(sin[0], sin[1]) and np.array_equal(spn[0], spn[1])
+    key = (tree_name, regime)
+    if key not in _REGIME_REF:
+        ref = dict(si=sin[0], sp=spn[0], sc=scn[0], res=[])
+        for b in range(B):
+            x64, g64, w64 = x[b].astype(np.float64), g[b].astype(np.float64), w[b].astype(np.float64)
+            want, saved = tfo.refine_forward(x64, w64, sin[0], spn[0], scn[0])
+            assert saved['WD'].min() >= 1
+            ref['res'].append((want, tfo.refine_backward_feature(g64, w64, sin[0], spn[0], scn[0], saved),
+                               tfo.refine_backward_weight(x64, g64, w64, sin[0], spn[0], scn[0], saved)))
+        _REGIME_REF[key] = ref
+    ref = _REGIME_REF[key]
+    assert np.array_equal(ref['si'], sin[0]) and np.array_equal(ref['sp'], spn[0]) and np.array_equal(ref['sc'], scn[0])
+    xd = torch.from_numpy(x).to(dev).requires_grad_(True)
+    wd = torch.from_numpy(w).to(dev).requires_grad_(True)
+    out = refine(xd, wd, si, sp, sc, False)
+    out.backward(torch.from_numpy(g).to(dev))
+    got, got_f, got_w = out.detach().cpu().numpy(), xd.grad.cpu().numpy(), wd.grad.cpu().numpy()
+    assert np.isfinite(got).all() and np.isfinite(got_f).all() and np.isfinite(got_w).all()
+    for b in range(B):
+        want, gf, gw = ref['res'][b]
+        assert np.isfinite(want).all() and np.isfinite(gf).all() and np.isfinite(gw).all()
+        assert np.abs(got[b] - want).max() <= 2e-5 * max(np.abs(want).max(), 1.0)
+        assert np.abs(got_f[b] - gf).max() <= 2e-5 * max(np.abs(gf).max(), 1.0)
+        assert np.abs(got_w[b] - gw).max() <= 1e-4 * max(np.abs(gw).max(), 1.0)
+        if regime == 'zeros':
+            assert np.array_equal(_bits(got[b]), _bits(x[b])) and np.array_equal(_bits(got_f[b]), _bits(g[b]))
+        elif regime == 'ones':
+            mean = x[b].astype(np.float64).sum(1).astype(np.float32) / np.float32(V)
+            gmean = g[b].astype(np.float64).sum(1).astype(np.float32) / np.float32(V)
+            assert np.array_equal(_bits(got[b]), _bits(np.repeat(mean[:, None], V, 1)))
+            assert np.array_equal(_bits(got_f[b]), _bits(np.repeat(gmean[:, None], V, 1)))
+        elif regime == 'cut':
+            comp = R.components(w[b], spn[0])
+            exact = np.empty((C, V), np.float32)
+            exact[:, sin[0]] = R.component_mean_f32(x[b][:, sin[0]], comp)[:, comp]
+            assert np.array_equal(_bits(got[b]), _bits(exact))
+
+
+@pytest.mark.parametrize('regime', R.REGIMES)
+@pytest.mark.parametrize('tree', ['mst16x16', 'strip256'])
+def test_refine_weight_regimes(built, dev, tree, regime):
+    """the LDS-resident kernels (tree_down_jump's composed maps) on weights of exactly 0, exactly 1 and subnormals (_run_weight_regime)"""
+    _run_weight_regime(dev, tree, regime)
 
 
 def test_tree_filter_errors(built, dev):
@@ -488,11 +655,55 @@ def test_large_refine_forward_backward_vs_oracle(built, dev, low, large_form):
             assert np.abs(wd.grad[b].cpu().numpy() - gw).max() <= 1e-4 * max(np.abs(gw).max(), 1.0)
 
 
-@pytest.mark.parametrize('shape', ['strip', 'comb', 'bushy'])
-def test_large_refine_tree_shapes(built, dev, shape, large_form):
+@pytest.mark.parametrize('regime', R.REGIMES)
+@pytest.mark.parametrize('tree', ['mst128x128', 'strip16384'])
+def test_large_refine_weight_regimes(built, dev, tree, regime, large_form):
+    """the workspace kernels, both forms (the depth-free pass multiplies weight products over 2^k levels: 14 rounds on the strip), on
+    weights of exactly 0, exactly 1 and subnormals (_run_weight_regime).  'ones' on the strip is the one case here in which a node 8192
+    levels down still counts: with any weight below 1 the product over that many levels has underflowed, so a late doubling round that
+    is lost (or reads the wrong buffer) changes nothing a tolerance can see -- only this case does."""
+    _run_weight_regime(dev, tree, regime)
+
+
+def test_large_tree_filter_module_gradients(built, dev, large_form):
+    """MinimumSpanningTree + TreeFilter2D(groups=2) just past the LDS-resident limit (101 x 102 = 10302 vertices), low_tree=False:
+    forward, feature gradient and the embedding gradient against the fp64 reference, in both forms of the large kernels"""
+    from boxinstseg_amd import MinimumSpanningTree, TreeFilter2D
+    rng = np.random.default_rng(31)
+    B, C, Ce, H, W = 1, 4, 4, 101, 102
+    assert H * W > 10200
+    guide = rng.standard_normal((B, 3, H, W)).astype(np.float32)
+    feat = rng.standard_normal((B, C, H, W)).astype(np.float32)
+    emb = (rng.standard_normal((B, Ce, H, W)) * 0.3).astype(np.float32)
+    gout = rng.standard_normal((B, C, H, W)).astype(np.float32)
+    tree = MinimumSpanningTree(TreeFilter2D.norm2_distance)(torch.from_numpy(guide).to(dev))
+    fd = torch.from_numpy(feat).to(dev).requires_grad_(True)
+    ed = torch.from_numpy(emb).to(dev).requires_grad_(True)
+    tf2 = TreeFilter2D(groups=2)
+    out = tf2(fd, ed, tree, low_tree=False)
+    out.backward(torch.from_numpy(gout).to(dev))
+    key = 'module101x102'
+    if key not in _REGIME_REF:
+        info = {}
+        _REGIME_REF[key] = (tree.cpu().numpy(), R.module_reference(feat, emb, tree.cpu().numpy(), 2, False, tf2.sigma, gout, info), info)
+    t0, (want, want_f, want_e), info = _REGIME_REF[key]
+    assert np.array_equal(t0, tree.cpu().numpy())
+    assert np.abs(out.detach().cpu().numpy() - want).max() <= 3e-5 * max(np.abs(want).max(), 1.0)
+    assert np.abs(fd.grad.cpu().numpy() - want_f).max() <= 3e-5 * max(np.abs(want_f).max(), 1.0)
+    _check_embedding_grad('module 101x102, 2 groups', ed.grad.cpu().numpy(), want_e, info['gw_absmax'])
+
+
+def test_large_tree_filter_module_default_low_tree(built, dev, large_form):
+    _default_module_case(dev, 1, 101, 102, 22)
+
+
+@pytest.mark.parametrize('shape,low', [pytest.param(s, lw, id=s if lw else s + '-weight_grad')
+                                       for lw in (True, False) for s in ('strip', 'comb', 'bushy')])
+def test_large_refine_tree_shapes(built, dev, shape, low, large_form):
     """The extremes of the depth-free leaf->root pass: a 1 x V strip (V levels of one node: every doubling round is effective), a comb
     (long teeth, levels up to 120 nodes wide, long descendant ranges near the root), a bushy random tree (few levels, wide ranges:
-    the whole-wave sums) -- forward and the feature gradient against the fp64 oracle, in both forms."""
+    the whole-wave sums) -- forward and the feature gradient against the fp64 oracle, in both forms; with low=False the weights are a
+    leaf too, and their gradient (the other backward launch, which also produces the feature gradient) is compared."""
     from boxinstseg_amd import bfs, refine
     rng = np.random.default_rng({'strip': 1, 'comb': 2, 'bushy': 3}[shape])
     if shape == 'strip':
@@ -523,13 +734,18 @@ def test_large_refine_tree_shapes(built, dev, shape, large_form):
     g = rng.standard_normal((1, C, V)).astype(np.float32)
     w = rng.uniform(0.55, 1.0, (1, V)).astype(np.float32)          # weights in sorted order (refine.cu: weight[0] is unused)
     xd = torch.from_numpy(x).to(dev).requires_grad_(True)
-    out = refine(xd, torch.from_numpy(w).to(dev), si, sp, sc, True)
+    wd = torch.from_numpy(w).to(dev).requires_grad_(not low)
+    out = refine(xd, wd, si, sp, sc, low)
     out.backward(torch.from_numpy(g).to(dev))
     want, saved = tfo.refine_forward(x[0].astype(np.float64), w[0].astype(np.float64), sin[0], spn[0], scn[0])
     assert np.isfinite(want).all()
     assert np.abs(out[0].detach().cpu().numpy() - want).max() <= 2e-5 * max(np.abs(want).max(), 1.0)
     gf = tfo.refine_backward_feature(g[0].astype(np.float64), w[0].astype(np.float64), sin[0], spn[0], scn[0], saved)
     assert np.abs(xd.grad[0].cpu().numpy() - gf).max() <= 2e-5 * max(np.abs(gf).max(), 1.0)
+    if not low:
+        gw = tfo.refine_backward_weight(x[0].astype(np.float64), g[0].astype(np.float64), w[0].astype(np.float64), sin[0], spn[0], scn[0],
+                                        saved)
+        assert np.abs(wd.grad[0].cpu().numpy() - gw).max() <= 1e-4 * max(np.abs(gw).max(), 1.0)
 
 
 def test_large_refine_vs_reference_kernels_live_200x304(built, dev):
