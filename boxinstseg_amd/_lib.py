@@ -355,6 +355,21 @@ def status_string(status: int) -> str:
     return load().bxi_status_string(status).decode()
 
 
+EVAL1_PLAN_FIELDS = ('taken', 'merge', 'table_last', 'n_stream', 'n_pool', 'n_pb', 'n_tb', 'grid')
+
+
+def eval1_plan(B: int, N: int, h: int, w: int, dilation: int = 2, flags: int = 0, stream: int = 0) -> dict:
+    """The form bxi_boxinst_eval_f32 would launch for this shape (include/boxinst_hip_plan.h: bxi_dev_eval1_plan, a developer query
+    that belongs to no ABI family: it launches nothing).  Raises with the status the evaluation would refuse the shape with."""
+    fn = load().bxi_dev_eval1_plan
+    fn.restype, fn.argtypes = c_int, [c_int, c_int, c_int, c_int, c_int, C.c_uint, c_void_p, c_void_p]
+    out = (c_int * len(EVAL1_PLAN_FIELDS))()
+    rc = fn(B, N, h, w, dilation, flags, stream, C.cast(out, c_void_p))
+    if rc != 0:
+        raise RuntimeError(f'bxi_dev_eval1_plan: {STATUS.get(rc, rc)}')
+    return dict(zip(EVAL1_PLAN_FIELDS, out))
+
+
 class BoxInstHipError(RuntimeError):
     def __init__(self, fn: str, status: int):
         self.status = status

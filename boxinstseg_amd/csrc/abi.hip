@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include "dynamic_head_device.hpp"
 #include "../../include/boxinst_hip_dev.h"
+#include "../../include/boxinst_hip_plan.h"
 #include <atomic>
 #include <cstdlib>
 
@@ -20,6 +21,7 @@ int eval_ws_init(void* workspace, size_t bytes, void* stream);
 int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bxi_instances* in, int dil, float warmup, const float* up_prj,
                       const float* up_pw, float* losses, float* g_logits, void* state, void* workspace, size_t workspace_bytes, unsigned flags,
                       void* stream, const DynArgs* head = nullptr, int head_C = 0);
+int eval1_plan_query(int B, int N, int h, int w, int dil, unsigned flags, void* stream, int* out);
 int launch_targets(const bxi_image_batch* batch, const float* const* boxes_per_img_host, const int* gt_count_host, int stride, int dil, float color_thresh,
                    void* workspace, size_t workspace_bytes, void* stream);
 int launch_rescale(const bxi_instances* in, const float* g_prj, const float* g_pw, int dil, const void* state, float* g_logits, void* stream);
@@ -55,6 +57,9 @@ void bxi_dev_set_launch_hook(bxi_launch_hook hook, void* user) {
     bxi::g_hook.store(hook, std::memory_order_release);
 }
 void bxi_dev_set_tree_level_walk(int on) { bxi::dev_set_tree_level_walk(on); }
+int bxi_dev_eval1_plan(int B, int N, int h, int w, int dilation, unsigned int flags, void* stream, int* out8) {
+    return bxi::eval1_plan_query(B, N, h, w, dilation, flags, stream, out8);
+}
 
 int bxi_check_device(int ordinal) {
     int count = 0;

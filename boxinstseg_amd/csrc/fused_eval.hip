@@ -148,8 +148,13 @@ __global__ __launch_bounds__(256, pair_occ(D, R)) void pair_kernel(const float* 
 }
 
 // ---- the single-launch form ---------------------------------------------------------------------------------------------------
-// All roles in ONE grid, in this order:  [stream blocks (their first waves write the table)][pool blocks][predicate blocks][reducer][N leaders][tile blocks][finisher].
-// Workgroups are dispatched in grid order and every wait is for a workgroup EARLIER in the grid:
+// All roles in ONE grid, in this order:  [stream blocks (the table is a duty of some of their waves)][pool blocks][predicate blocks][reducer][N leaders][tile blocks][finisher].
+// The table wave k (entries 64 k .. 64 k + 63) is wave 0 of stream block k -- or, where the stream blocks stay on and an instance's last band
+// leaves a wave without rows, the last wave of instance k's last band: that one writes it at once, the other behind its 8 KB of zero-fill.
+// Workgroups are dispatched in grid order and every wait is for a workgroup EARLIER in the grid -- with two exceptions, both of stream
+// workgroups that stay on and both only in forms where every stream workgroup holds a slot from the start and at least half of the slots
+// stay free: their tile waves wait for predicate workgroups later in the grid, and, with the table in the last bands, for a table wave
+// in a stream workgroup that may stand behind their own (it waits for nobody):
 //   table, stream, pool   wait for nobody;
 //   leader n              for the table entry n and the band flags of instance n (stream blocks);
 //   predicate wave        for the Lab pixels it reads (pool blocks; 16-byte records carrying the evaluation's tag) and the table;
@@ -207,12 +212,22 @@ __global__ __launch_bounds__(256, (R == 4 ? kOneOcc : kLongOcc)) void eval1_kern
     bool stayed = false;
     if (role == 0) {
         BXI_TW(0, tix, 0);
-        // the table is the first duty of the first stream workgroups' first waves (wave k of the table in workgroup k): a workgroup
-        // of its own would be the one workgroup too many for the front half to be resident at once at the headline size
+        // the table is a duty of stream waves: a workgroup of its own would be the one workgroup too many for the front half to be
+        // resident at once at the headline size.  Wave k of the table (entries 64 k .. 64 k + 63) is wave 0 of stream workgroup k -- or
+        // (merge bit 1, the host's choice: plan_eval1, table_last) the last wave of instance k's last band, which has no rows there: no
+        // zero-fill stores to drain ahead of the table's own, no loads to wait for, so the table -- the first thing every leader,
+        // predicate wave and tile wave polls -- is in memory as the launch starts, and stream workgroup 0, whose waves stay on as tile
+        // waves, ends with the others.  Safe: the table wave waits for nobody, and the host takes this placement only where every stream
+        // workgroup holds a slot from the start, so a staying wave that polls an entry written LATER in the grid never holds the slot the
+        // writer needs.
         const LogitRows rows = {a.logits + (int64_t)(idx / Sn) * a.h * a.w, a.w, vec & 1, vec >> 1};
         stream_block<true>(a, ws, g_logits, vec & 1, idx, reinterpret_cast<unsigned long long*>(smem), rows, tix, [&](Ws& w_) {
             w_ = with_tag(w_);
-            if (!READY && (threadIdx.x >> 6) == 0 && 64 * idx <= N) table_wave(a, pa.meta, D, R, w_, st, idx, false, 0, 0u);
+            if (READY) return;
+            // (two call sites on purpose: with one, behind a computed k, the forms that keep the table where it was -- 64 instances, a
+            // shared device -- ran 0.3 us slower in this kernel; profiles/NOTES.md R23-1)
+            if ((threadIdx.x >> 6) == 0 && 64 * idx <= N && !(merge & 2)) table_wave(a, pa.meta, D, R, w_, st, idx, false, 0, 0u);
+            if ((threadIdx.x >> 6) == kWaves - 1 && (merge & 2) && idx % Sn == Sn - 1 && 64 * (idx / Sn) <= N) table_wave(a, pa.meta, D, R, w_, st, idx / Sn, false, 0, 0u);
         });
         BXI_TW(0, tix, 7);
         if (!merge) return;
@@ -220,8 +235,10 @@ __global__ __launch_bounds__(256, (R == 4 ? kOneOcc : kLongOcc)) void eval1_kern
         // table -> tile -> logits -> per-pixel chain runs while the pool workgroups finish instead of behind a slot that has to come
         // free first.  (It now waits for predicate workgroups LATER in the grid.  Those wait only for pool workgroups, which wait for
         // nobody, and the host launches this form only while the stream workgroups leave at least half of the slots free: a
-        // predicate workgroup always finds a slot.)
-        __syncthreads();                                                   // the column-partial LDS becomes the tile waves' scratch
+        // predicate workgroup always finds a slot.  With the table in the last bands it also waits for a table wave of a stream
+        // workgroup that may stand later in the grid: that one is resident too -- the stream workgroups are at most a quarter of the
+        // slots here -- and writes the table before it waits for anything.)
+        __syncthreads();                                                  // the column-partial LDS becomes the tile waves' scratch
         role = 4;
         stayed = true;
         idx -= n_stream;                                                   // tile workgroup index idx + n_stream below
@@ -559,6 +576,98 @@ int launch_targets(const bxi_image_batch* batch, const float* const* boxes_per_i
     return check_launch();
 }
 
+// ---- the single launch: whether an evaluation is ONE eval1_kernel launch, and its grid ------------------------------------------------
+// A function of the shape, the flags and the stream alone; launch_fused_eval launches what it says and bxi_dev_eval1_plan reports it.
+struct Eval1Plan {
+    int taken;               // the evaluation is one eval1_kernel launch
+    int long_form;           // 8-row tiles, three workgroups per CU, pool workgroups first
+    int merge;               // the stream workgroups stay on as the first tile workgroups
+    int table_last;          // the table is written from the instances' last bands (eval1_kernel: the stream role's hook)
+    int n_tabw, n_stream, n_pool, n_pb, n_tb;      // workgroups per role
+    unsigned grid;
+    size_t lds;
+};
+// eligible: no head-fused first launch, the image pooled in the launch, a colour threshold above 0
+static Eval1Plan plan_eval1(int N, int h, int w, int n_items, int dil, int R, int64_t cap, unsigned flags, bool ready, bool eligible, hipStream_t s) {
+    Eval1Plan p = {};
+    const int n_tab = ((N + 64) / 64 + kWaves - 1) / kWaves;
+    const int Sn = (h + kSBlk - 1) / kSBlk;
+    const int n_stream = N * Sn;
+    const size_t lds_stream = std::max(kPoolLds, 8 * (size_t)kWaves * w);
+    auto lds_pair_of = [&](int kern) { return std::max((size_t)kWaves * tile_wave_lds(dil, R, kern), 2 * sizeof(float) * (size_t)(h + w) + 16); };
+    const bool whole_device = stream_cus(s, device_cus()) >= device_cus();                      // a CU-masked stream has fewer
+    // The single launch pays off while its front half (stream + pool workgroups) is resident at once: measured 24.8 vs 27.0 us at
+    // 64 instances, 35.1 vs 33.9 at 96, 45.1 vs 39.4 at 128 (200 x 256 maps) -- hence: stream workgroups <= half the slots.
+    const int one_slots = kOneOcc * device_cus();
+    const bool one_fits = 2 * (int64_t)n_stream <= one_slots && whole_device;
+    // (built for dilation <= 2: the single launch needs four workgroups per CU, and at dilation 3 the tile role does not fit 128 VGPRs)
+    // Two shapes of the single launch: the SHORT form (4-row tiles, four workgroups per CU, the stream workgroups staying on as the first tile
+    // workgroups) while its front half is resident at once; the LONG form (8-row tiles, three per CU, pool workgroups first, nobody waits for a
+    // later workgroup) for many instances, where the short form's tile waves would each walk several tiles one after the other.
+    // The long form only with the targets ready: with the image side in the launch, three workgroups per CU slow the front half down by what
+    // the kernel boundary costs.  So the library takes it where it is asked to (BXI_EVAL_SINGLE_LAUNCH with 8-row tiles) and, with the targets
+    // ready, from kLongFrom on: 21.6 against 23.9 us for two launches (R6-14)
+    const bool long_form = R == 8 && dil <= 2 && ready && ((flags & kFlagSingle) || (N >= kLongFrom && whole_device && !(flags & kFlagShared)));
+    // (targets ready: the short single launch while its stream workgroups are a quarter of the slots -- 14.1 vs 14.4-14.9 us for two launches at 32
+    // instances; at 64 two launches take 18.3 against 18.7 us: R6-14)
+    const bool short_ok = one_fits && !(ready && 4 * (int64_t)n_stream > one_slots);
+    p.lds = std::max(lds_stream, lds_pair_of(ready ? kTilesOneReady : kTilesOne));
+    p.long_form = long_form ? 1 : 0;
+    p.n_stream = n_stream;
+    p.taken = !(flags & kFlagTwo) && (short_ok || (flags & kFlagSingle) || long_form) && eligible && (R == 4 || long_form) && dil <= 2 &&
+              p.lds <= 36 * 1024;                                         // (four workgroups per CU must fit)
+    if (!p.taken) return p;
+    const int slots = long_form ? kLongOcc * device_cus() : one_slots;
+    // the front half (table, stream, pool) should fill the GPU exactly once: a pool workgroup takes several items (never more than two in
+    // the long form, as in the first launch of the two-launch form)
+    const int front = slots - n_stream;
+    p.n_pool = ready ? 0 : pool_wgs(n_items, front > slots / 4 ? front : slots / 4, long_form ? 2 : 0);
+    p.n_pb = ready ? 0 : pred_wgs(n_items, slots / 2);
+    // One tile per wave while the slots last: a wave that walks two tiles runs two ~7 us dependent chains one after the other.  The tile
+    // workgroups are the LAST workgroups of the grid and wait only for earlier ones, so nothing else depends on their number.
+    p.n_tb = tile_wgs(cap, slots);
+    // the stream workgroups stay on as the first tile workgroups (only while they leave half of the slots to the rest of the grid)
+    // ... unless evaluations run on SEVERAL streams at once: each would hold its stream workgroups' slots while waiting, and three
+    // or four of them leave no room for anybody's pool workgroups (measured: 2.4 ms per evaluation with four streams in flight,
+    // against 10 us without the staying-on).  The library cannot see what else runs on the device and does not guess: the CALLER
+    // says so (BXI_EVAL_SHARED_DEVICE; boxinstseg_amd/functional.py sets it once a second stream has been
+    // seen on the device).  A launch that is being captured into a graph may be replayed next to anything: no staying-on either.
+    // ... and only while they are at most a QUARTER of the slots: at 64 instances (448 of 1024) the staying-on costs 0.3 us (21.65 vs 21.35 us, their
+    // slots are what the pool workgroups -- three items each then -- are short of); at 32 instances it is worth 0.05 us (R6-12)
+    p.merge = !long_form && one_fits && 4 * n_stream <= slots && !(flags & kFlagShared) && !stream_is_capturing(s) ? 1 : 0;
+    if (p.merge) p.n_tb = p.n_tb > n_stream ? p.n_tb - n_stream : 0;
+    // The table from the instances' last bands: where the stream workgroups stay on -- every one of them then holds a slot from the start
+    // (4 n_stream <= slots), so a staying wave that polls the table never holds the slot its writer needs -- and the last band of an
+    // instance leaves its last wave without rows.  The image side in the launch only (with the targets ready the table has workgroups
+    // of its own).
+    p.table_last = p.merge && !ready && h - (Sn - 1) * kSBlk <= (kWaves - 1) * kSRows ? 1 : 0;
+    p.n_tabw = ready ? n_tab : 0;
+    p.grid = (unsigned)(p.n_tabw + n_stream + p.n_pool + p.n_pb + 1 + N + p.n_tb + 1);
+    return p;
+}
+
+static int eval_tile_rows(unsigned flags, int N, int dil) { return (flags & kFlagRows8) ? 8 : ((flags & kFlagRows4) ? 4 : tile_rows_for(N, dil)); }
+static int64_t eval_items(int B, int h, int w) { return (int64_t)B * h * ((w + 63) / 64); }      // one item = a pooled row segment of 64 pixels
+
+// bxi_dev_eval1_plan (developer query, tests): the plan of an evaluation of N instance maps [h, w] over B images whose image side is
+// pooled in the launch (stride 4, aligned rows), colour threshold above 0, no head -- from the functions the launch itself asks.
+// out[8]: taken, merge, table_last, n_stream, n_pool, n_pb, n_tb, grid
+int eval1_plan_query(int B, int N, int h, int w, int dil, unsigned flags, void* stream, int* out) {
+    if (!out) return BXI_ERR_NULL_POINTER;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    if (N == 0) return BXI_OK;                 // no instances: the evaluation writes two zeros, none of these kernels runs
+    if (B <= 0 || B > BXI_MAX_IMAGES || N < 0 || N >= kMaxInst || h <= 0 || w <= 0 || h > 65535 || w > 65535) return BXI_ERR_BAD_SHAPE;
+    if (!fused_eval_supported(dil)) return BXI_ERR_UNSUPPORTED;
+    const int R = eval_tile_rows(flags, N, dil);
+    const int64_t cap = eval_cap(N, h, w, dil, R);
+    const int64_t n_items64 = eval_items(B, h, w);
+    if (cap >= (1 << 24) || n_items64 > 0x7fffffffLL) return BXI_ERR_BAD_SHAPE;
+    const Eval1Plan p = plan_eval1(N, h, w, (int)n_items64, dil, R, cap, flags, (flags & kFlagTargetsReady) != 0, true, as_stream(stream));
+    const int v[8] = {p.taken, p.merge, p.table_last, p.n_stream, p.n_pool, p.n_pb, p.n_tb, (int)p.grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return BXI_OK;
+}
+
 // One evaluation: one launch (eval1) or two (prep, pair).
 int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bxi_instances* in, int dil, float warmup, const float* up_prj,
                  const float* up_pw, float* losses, float* g_logits, void* state, void* workspace, size_t workspace_bytes, unsigned flags,
@@ -611,14 +720,14 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     const int nt_stream = (int64_t)a.N * a.h * a.w * 4 >= ((int64_t)kNtStreamFromMB << 20) ? 2 : 0;
     const int vec = (((a.w & 3) == 0 && (reinterpret_cast<uintptr_t>(a.logits) & 15) == 0 &&
                       (!g_logits || (reinterpret_cast<uintptr_t>(g_logits) & 15) == 0)) ? 1 : 0) | nt_stream;
-    const int R = (flags & kFlagRows8) ? 8 : ((flags & kFlagRows4) ? 4 : tile_rows_for(a.N, dil));
+    const int R = eval_tile_rows(flags, a.N, dil);
     const int64_t cap = eval_cap(a.N, a.h, a.w, dil, R);
     if (cap >= (1 << 24)) return BXI_ERR_BAD_SHAPE;     // the table packs a tile prefix into 24 bits
     const HostPred pr = host_pred(color_thresh);
     if (ready && pr.zero_bit) return BXI_ERR_UNSUPPORTED;       // (bxi_boxinst_targets_f32 refuses thresholds <= 0 as well)
     ValidCells vc = {};
     valid_cells_of(pa, batch->B, a.stride, a.h, a.w, vc);
-    const int64_t n_items64 = (int64_t)batch->B * a.h * ((a.w + 63) / 64);
+    const int64_t n_items64 = eval_items(batch->B, a.h, a.w);
     if (n_items64 > 0x7fffffffLL) return BXI_ERR_BAD_SHAPE;
     const int n_items = (int)n_items64;
     const int spin_limit = (flags & kFlagGiveUp) ? -1 : kSpinLimit;
@@ -632,52 +741,14 @@ int launch_fused_eval(const bxi_image_batch* batch, float color_thresh, const bx
     auto lds_pair_of = [&](int kern) { return std::max((size_t)kWaves * tile_wave_lds(dil, R, kern), 2 * sizeof(float) * (size_t)(a.h + a.w) + 16); };
     const size_t lds_pair = lds_pair_of(kTilesPair);
     const int cus = stream_cus(s, device_cus());                      // a CU-masked stream has fewer
-    const bool whole_device = cus >= device_cus();
 
-    // ---- the single-launch form ---------------------------------------------------------------------------------------
-    // The single launch pays off while its front half (stream + pool workgroups) is resident at once: measured 24.8 vs 27.0 us at
-    // 64 instances, 35.1 vs 33.9 at 96, 45.1 vs 39.4 at 128 (200 x 256 maps) -- hence: stream workgroups <= half the slots.
-    const int one_slots = kOneOcc * device_cus();
-    const bool one_fits = 2 * (int64_t)n_stream <= one_slots && whole_device;
-    // (built for dilation <= 2: the single launch needs four workgroups per CU, and at dilation 3 the tile role does not fit 128 VGPRs)
-    // Two shapes of the single launch: the SHORT form (4-row tiles, four workgroups per CU, the stream workgroups staying on as the first tile
-    // workgroups) while its front half is resident at once; the LONG form (8-row tiles, three per CU, pool workgroups first, nobody waits for a
-    // later workgroup) for many instances, where the short form's tile waves would each walk several tiles one after the other.
-    // The long form only with the targets ready: with the image side in the launch, three workgroups per CU slow the front half down by what
-    // the kernel boundary costs.  So the library takes it where it is asked to (BXI_EVAL_SINGLE_LAUNCH with 8-row tiles) and, with the targets
-    // ready, from kLongFrom on: 21.6 against 23.9 us for two launches (R6-14)
-    const bool long_form = R == 8 && dil <= 2 && ready && ((flags & kFlagSingle) || (a.N >= kLongFrom && whole_device && !(flags & kFlagShared)));
-    // (targets ready: the short single launch while its stream workgroups are a quarter of the slots -- 14.1 vs 14.4-14.9 us for two launches at 32
-    // instances; at 64 two launches take 18.3 against 18.7 us: R6-14)
-    const bool short_ok = one_fits && !(ready && 4 * (int64_t)n_stream > one_slots);
-    const size_t lds_one = std::max(lds_stream, lds_pair_of(ready ? kTilesOneReady : kTilesOne));
-    if (!(flags & kFlagTwo) && (short_ok || (flags & kFlagSingle) || long_form) && !head && pooled_in_launch && (R == 4 || long_form) && dil <= 2 &&
-        !pr.zero_bit && lds_one <= 36 * 1024) {                       // (four workgroups per CU must fit)
-        const int slots = long_form ? kLongOcc * device_cus() : one_slots;
-        // the front half (table, stream, pool) should fill the GPU exactly once: a pool workgroup takes several items (never more than two in
-        // the long form, as in the first launch of the two-launch form below)
-        const int front = slots - n_stream;
-        const int n_pool = ready ? 0 : pool_wgs(n_items, front > slots / 4 ? front : slots / 4, long_form ? 2 : 0);
-        const int n_pb = ready ? 0 : pred_wgs(n_items, slots / 2);
-        // One tile per wave while the slots last: a wave that walks two tiles runs two ~7 us dependent chains one after the other.  The tile
-        // workgroups are the LAST workgroups of the grid and wait only for earlier ones, so nothing else depends on their number.
-        int n_tb = tile_wgs(cap, slots);
-        // the stream workgroups stay on as the first tile workgroups (only while they leave half of the slots to the rest of the grid)
-        // ... unless evaluations run on SEVERAL streams at once: each would hold its stream workgroups' slots while waiting, and three
-        // or four of them leave no room for anybody's pool workgroups (measured: 2.4 ms per evaluation with four streams in flight,
-        // against 10 us without the staying-on).  The library cannot see what else runs on the device and does not guess: the CALLER
-        // says so (BXI_EVAL_SHARED_DEVICE; boxinstseg_amd/functional.py sets it once a second stream has been
-        // seen on the device).  A launch that is being captured into a graph may be replayed next to anything: no staying-on either.
-        // ... and only while they are at most a QUARTER of the slots: at 64 instances (448 of 1024) the staying-on costs 0.3 us (21.65 vs 21.35 us, their
-        // slots are what the pool workgroups -- three items each then -- are short of); at 32 instances it is worth 0.05 us (R6-12)
-        const int merge = !long_form && one_fits && 4 * n_stream <= slots && !(flags & kFlagShared) && !stream_is_capturing(s) ? 1 : 0;
-        if (merge) n_tb = n_tb > n_stream ? n_tb - n_stream : 0;
-        const int n_tabw = ready ? n_tab : 0;
-        const unsigned grid = (unsigned)(n_tabw + n_stream + n_pool + n_pb + 1 + a.N + n_tb + 1);
+    // ---- the single-launch form (plan_eval1 above decides and sizes it) ------------------------------------------------------
+    const Eval1Plan pl = plan_eval1(a.N, a.h, a.w, n_items, dil, R, cap, flags, ready != 0, !head && pooled_in_launch && !pr.zero_bit, s);
+    if (pl.taken) {
         constexpr decltype(&eval1_kernel<1, 8, true>) eval1_kernels[2][3] = {{eval1_kernel<1, 8, true>, eval1_kernel<1, 4, true>, eval1_kernel<1, 4, false>},
                                                                              {eval1_kernel<2, 8, true>, eval1_kernel<2, 4, true>, eval1_kernel<2, 4, false>}};
-        BXI_LAUNCH(ready ? "eval1_ready" : "eval1", s, eval1_kernels[dil - 1][long_form ? 0 : (ready ? 1 : 2)], dim3(grid), dim3(256), lds_one, s, pa, n_pool, n_items, n_pb, n_tb, a, ws, st, vc, up_prj,
-                   up_pw, warmup, pr.n2max, spin_limit, losses, g_logits, vec, merge, ready, key, n_tabw);
+        BXI_LAUNCH(ready ? "eval1_ready" : "eval1", s, eval1_kernels[dil - 1][pl.long_form ? 0 : (ready ? 1 : 2)], dim3(pl.grid), dim3(256), pl.lds, s, pa, pl.n_pool, n_items, pl.n_pb, pl.n_tb, a, ws, st, vc, up_prj,
+                   up_pw, warmup, pr.n2max, spin_limit, losses, g_logits, vec, pl.merge | (pl.table_last ? 2 : 0), ready, key, pl.n_tabw);
         return check_launch();
     }
 
