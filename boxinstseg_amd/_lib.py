@@ -132,6 +132,10 @@ SIGNATURES = {
                                                     c_void_p, c_size_t, c_void_p]),
 }
 
+# csrc/meanfield.hip: kMfManyItems.  bxi_meanfield_forward_f32 runs four (instance, row, segment) items per wave when N * H * ceil(W / 64)
+# exceeds this, one otherwise (tests/test_host_meanfield_decided.py holds the two together; tests/test_gpu_meanfield_paths.py runs both sides)
+MF_MANY_ITEMS = 32768
+
 # include/boxinst/boxinst_hip_post.h (test-time post-processing of the SOLOv2-style heads)
 NMS_KERNELS = {'gaussian': 0, 'linear': 1}
 NMS_MAX_CANDIDATES = 2048

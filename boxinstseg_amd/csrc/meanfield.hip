@@ -78,6 +78,7 @@ struct MfArgs {
 };
 
 constexpr int kMfWaves = 4;   // waves per workgroup of the per-item kernels
+constexpr int kMfManyItems = 32768;   // more (instance, row, segment) items than this: 4 items per wave (_lib.MF_MANY_ITEMS)
 // IPW = consecutive items per wave: 4 when there are many items (4x fewer workgroups to dispatch), 1 when few
 // (all the parallelism there is)
 
@@ -464,7 +465,7 @@ int bxi_meanfield_forward_f32(const float* kernel, int B, int H, int W, int ksiz
     a.gamma = gamma;
     a.vlo = (float)((double)(H * W) * 0.05); a.vhi = (float)((double)(H * W) * 0.95);
     hipStream_t s = bxi::as_stream(stream);
-    const bool many = (int64_t)N * H * a.segs > 32768;
+    const bool many = (int64_t)N * H * a.segs > bxi::kMfManyItems;
     const int ipw = many ? 4 : 1, per_wg = bxi::kMfWaves * ipw;
     const dim3 grid((unsigned)((H * a.segs + per_wg - 1) / per_wg), (unsigned)N), block(64 * bxi::kMfWaves);
     if (many) BXI_LAUNCH("mf_init", s, bxi::mf_init_kernel<4>, grid, block, 0, s, a);

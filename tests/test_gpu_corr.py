@@ -177,7 +177,9 @@ def test_meanfield_takes_the_produced_iiu(dev):
     Ko = do.meanfield_kernel(feat, 3, 2.0, 0.5, 30.0)
     want, wv = do.meanfield_forward(Ko, x, t, 10, 0.1, G['plain_iiu'].astype(np.float32), 0.01)
     bad = int((ret.squeeze(1).cpu().numpy() != want).sum())
-    assert bad <= max(1, int(2e-4 * want.size)), f'{bad} of {want.size} labels differ'      # the bound of test_gpu_discobox.py:test_meanfield_fuzz
+    # the kernel values and the iiu are the device's here (expf ulps apart from the oracle's), which tests/mf_decided.py does not model: the
+    # bound of the second half of test_gpu_discobox.py::test_meanfield_reference_fixture
+    assert bad <= max(1, int(2e-4 * want.size)), f'{bad} of {want.size} labels differ'
     if bad == 0:
         assert np.array_equal(valid.cpu().numpy(), wv)
 

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import discobox_oracle as do
+from tests import mf_decided as M
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
@@ -44,44 +45,37 @@ def test_meanfield_reference_fixture(built, dev, case):
     assert int((ret2[:, 0].cpu().numpy() != g[f'{case}_ret']).sum()) <= 2e-4 * ret2.numel()
 
 
-@pytest.mark.parametrize('H,W,n,ks,iters,base', [(100, 136, 12, 3, 10, 0.10), (200, 304, 6, 3, 10, 0.10), (64, 64, 3, 5, 3, 0.45),
-                                                 (37, 65, 4, 3, 0, 0.10), (50, 129, 5, 3, 1, 0.30)])
+@pytest.mark.parametrize('H,W,n,ks,iters,base', M.VS_ORACLE_PARAMS)
 def test_meanfield_vs_oracle(built, dev, H, W, n, ks, iters, base):
-    """Seeded image-like features, several instances over two images (img_inds), step-by-step agreement."""
+    """Seeded image-like features, several instances over two images (img_inds; tests/mf_decided.py::recipe): every label is the oracle's.
+    (Were a label of these inputs undecided -- tests/test_host_meanfield_decided.py prints that none is -- the steps would be compared one
+    at a time on the decided ones.)"""
     from boxinstseg_amd import meanfield_forward, meanfield_kernel
-    rng = np.random.default_rng(H * 1000 + W)
-    yy, xx = np.mgrid[0:H, 0:W]
-    feats = []
-    for b in range(2):
-        f = np.stack([np.sin(xx / (7.0 + b)) + 0.3 * np.cos(yy / 5.0), np.cos(xx / 9.0 + yy / 11.0), 0.5 * np.sin(yy / (4.0 + b))])
-        feats.append((f + 0.05 * rng.standard_normal(f.shape)).astype(np.float32))
-    feats = np.stack(feats)
+    d = M.recipe(n, H, W, ks)
+    feats, Ko, x, t, img = d['feats'], d['Ko'], d['x'], d['t'], d['img']
     K = meanfield_kernel(torch.from_numpy(feats).to(dev), ks, 2.0, 0.5, 30.0)
-    Ko = np.stack([do.meanfield_kernel(feats[b], ks, 2.0, 0.5, 30.0) for b in range(2)])
     assert (np.abs(K.cpu().numpy() - Ko) <= 4e-7 * np.abs(Ko) + 1e-37).all()
-    x = rng.uniform(0, 1, size=(n, H, W)).astype(np.float32)
-    t = np.zeros((n, H, W), np.uint8)
-    for i in range(n):
-        r0, c0 = int(rng.integers(0, H // 2)), int(rng.integers(0, W // 2))
-        t[i, r0:r0 + int(rng.integers(4, H // 2 + 1)), c0:c0 + int(rng.integers(4, W // 2 + 1))] = 1
-    t[0, :, :] = 1                                   # a target covering the whole map (touches every border)
-    img = rng.integers(0, 2, size=n)
+    assert t[0].all()                                # a target covering the whole map (touches every border)
     Kd = torch.from_numpy(Ko).to(dev)                # same kernel values on both sides: decisions must then agree
-    ret, valid = meanfield_forward(Kd, torch.from_numpy(x).to(dev), torch.from_numpy(t).to(dev), iters, base,
-                                   img_inds=torch.from_numpy(img).to(dev))
+    imgd = torch.from_numpy(img).to(dev)
+
+    def run(targets):
+        def call(xs, its):
+            ret, valid = meanfield_forward(Kd, torch.from_numpy(xs).to(dev), targets, its, base, img_inds=imgd)
+            return ret.cpu().numpy(), valid.cpu().numpy()
+        return call
     want = np.zeros_like(x); wv = np.zeros(n, np.float32)
     for b in range(2):
         m = img == b
         if m.any():
             want[m], wv[m] = do.meanfield_forward(Ko[b], x[m], t[m], iters, base)
-    bad = int((ret.cpu().numpy() != want).sum())
-    assert bad <= 1e-4 * want.size, f'{bad} of {want.size} labels differ'
-    if bad == 0:
-        assert np.array_equal(valid.cpu().numpy(), wv)
+    states, undecided = M.trajectory_by_image(Ko, img, x, t, iters, base)
+    assert np.array_equal(states[-1].astype(np.float32), want) and np.array_equal(M.valid_of(states[-1]), wv)
+    M.assert_labels(run(torch.from_numpy(t).to(dev)), x, t, states, undecided, f'{H}x{W}')
     # float targets give the same answer as uint8 targets
-    ret_f, _ = meanfield_forward(Kd, torch.from_numpy(x).to(dev), torch.from_numpy(t).float().to(dev), iters, base,
-                                 img_inds=torch.from_numpy(img).to(dev))
-    assert torch.equal(ret_f, ret)
+    M.assert_labels(run(torch.from_numpy(t).float().to(dev)), x, t, states, undecided, f'{H}x{W} float targets')
+    (ret, valid), (ret_f, valid_f) = run(torch.from_numpy(t).to(dev))(x, iters), run(torch.from_numpy(t).float().to(dev))(x, iters)
+    assert np.array_equal(ret_f, ret) and np.array_equal(valid_f, valid)
 
 
 @pytest.mark.parametrize('case', ['a', 'b', 'c'])
@@ -136,43 +130,24 @@ def test_discobox_errors_and_empty(built, dev):
     assert dice_loss(torch.zeros(0, 5, device=dev), torch.zeros(0, 5, device=dev)).shape == (0,)
 
 
-@pytest.mark.parametrize('seed', list(range(10)))
+@pytest.mark.parametrize('seed', M.FUZZ_SEEDS)
 def test_meanfield_fuzz(built, dev, seed):
     """Seeded sweep over map sizes (widths around the 64-pixel word boundary), kernel 3 / 5, iteration counts, bases, one or two
-    images, empty / full / thin targets, with and without inter_img_mask."""
+    images, empty / full / thin targets, with and without inter_img_mask (tests/mf_decided.py::fuzz_recipe): every label is the oracle's."""
     from boxinstseg_amd import meanfield_forward
-    rng = np.random.default_rng(4000 + seed)
-    H = int(rng.integers(2, 60)); W = int(rng.choice([1, 5, 63, 64, 65, 127, 128, 129, int(rng.integers(2, 200))]))
-    ks = int(rng.choice([3, 3, 5])); iters = int(rng.integers(0, 12)); base = float(rng.choice([0.05, 0.1, 0.3, 0.45]))
-    n = int(rng.integers(1, 9)); B = int(rng.integers(1, 3))
-    yy, xx = np.mgrid[0:H, 0:W]
-    feats = np.stack([np.stack([np.sin(xx / (5.0 + b)), np.cos(yy / 6.0 + xx / 9.0), 0.3 * np.sin(yy / 3.0)]) for b in range(B)])
-    feats = (feats + 0.1 * rng.standard_normal(feats.shape)).astype(np.float32)
-    Ko = np.stack([do.meanfield_kernel(feats[b], ks, 2.0, 0.5, 30.0) for b in range(B)])
-    x = rng.uniform(0, 1, size=(n, H, W)).astype(np.float32)
-    t = np.zeros((n, H, W), np.uint8)
-    for i in range(n):
-        kind = int(rng.integers(0, 5))
-        if kind == 0:
-            continue                                   # no target
-        if kind == 1:
-            t[i] = 1                                   # everything
-        elif kind == 2:
-            t[i, int(rng.integers(0, H)), :] = 1       # one row
-        else:
-            r0, c0 = int(rng.integers(0, H)), int(rng.integers(0, W))
-            t[i, r0:r0 + int(rng.integers(1, H + 1)), c0:c0 + int(rng.integers(1, W + 1))] = 1
-    img = rng.integers(0, B, size=n)
-    inter = rng.uniform(0, 20, size=(n, 2, H, W)).astype(np.float32) if rng.integers(0, 2) else None
-    ret, valid = meanfield_forward(torch.from_numpy(Ko).to(dev), torch.from_numpy(x).to(dev), torch.from_numpy(t).to(dev), iters, base,
-                                   img_inds=torch.from_numpy(img).to(dev),
-                                   inter_img_mask=None if inter is None else torch.from_numpy(inter).to(dev), gamma=0.01)
-    want = np.zeros_like(x); wv = np.zeros(n, np.float32)
-    for b in range(B):
+    d = M.fuzz_recipe(seed)
+    Ko, x, t, img, inter, iters, base = d['Ko'], d['x'], d['t'], d['img'], d['inter'], d['iters'], d['base']
+    Kd, td, imgd = torch.from_numpy(Ko).to(dev), torch.from_numpy(t).to(dev), torch.from_numpy(img).to(dev)
+    interd = None if inter is None else torch.from_numpy(inter).to(dev)
+
+    def run(xs, its):
+        ret, valid = meanfield_forward(Kd, torch.from_numpy(xs).to(dev), td, its, base, img_inds=imgd, inter_img_mask=interd, gamma=0.01)
+        return ret.cpu().numpy(), valid.cpu().numpy()
+    want = np.zeros_like(x); wv = np.zeros(d['n'], np.float32)
+    for b in range(Ko.shape[0]):
         m = img == b
         if m.any():
             want[m], wv[m] = do.meanfield_forward(Ko[b], x[m], t[m], iters, base, None if inter is None else inter[m], 0.01)
-    bad = int((ret.cpu().numpy() != want).sum())
-    assert bad <= max(1, int(2e-4 * want.size)), f'{bad} of {want.size} labels differ ({H}x{W} ks{ks} it{iters} base{base})'
-    if bad == 0:
-        assert np.array_equal(valid.cpu().numpy(), wv)
+    states, undecided = M.trajectory_by_image(Ko, img, x, t, iters, base, inter, 0.01)
+    assert np.array_equal(states[-1].astype(np.float32), want) and np.array_equal(M.valid_of(states[-1]), wv)
+    M.assert_labels(run, x, t, states, undecided, f'{d["H"]}x{d["W"]} ks{d["ks"]} it{iters} base{base}')
