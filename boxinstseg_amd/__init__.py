@@ -42,6 +42,10 @@ Public surface (mirrors the reference's for this path):
     pack_attn_mask                     : an existing bool attention mask [B*M,Q,S] or [Q,S] packed to a PackedAttnMask on the device
     masked_attention                   : the attention core of torch.nn.MultiheadAttention with that mask, forward and backward, no [Q,S] tensor
     MultiheadAttention                 <-> mmcv's module, the cross- and self-attention of Box2Mask's transformer decoder; ATTENTION, build_attention
+    instance_topk                      <-> softmax, topk and is_thing filter of MaskFormerFusionHead.instance_postprocess (one launch, defined order)
+    box2mask_instances                 <-> Box2Mask after the decoder: both F.interpolate, crop, ``> 0``, mask score, mask2bbox (no fp32 canvas)
+    MaskFormerFusionHead               <-> mmdet's panoptic_fusion_head of configs/box2mask (instance results; registered in HEADS)
+    box2mask_format_results            <-> the formatting loop of MaskFormer.simple_test (bbox2result, masks to numpy: one host copy, one sync)
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -62,6 +66,7 @@ from .roi_align import RoIAlign, corr_level, relu_and_l2_norm_feat, roi_align, r
 from .msda import MultiScaleDeformableAttention, multi_scale_deformable_attn, multi_scale_deformable_attn_fused
 from .solo_conv import solo_candidate_masks, solo_dynamic_masks, solo_dynamic_masks_pair
 from .masked_attn import MultiheadAttention, PackedAttnMask, attn_mask_bits, box2mask_attn_mask, masked_attention, pack_attn_mask
+from .inst_post import MaskFormerFusionHead, box2mask_format_results, box2mask_instances, instance_topk
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -80,5 +85,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level',
            'multi_scale_deformable_attn', 'multi_scale_deformable_attn_fused', 'MultiScaleDeformableAttention', 'ATTENTION', 'build_attention',
            'solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks',
-           'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention']
+           'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention',
+           'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results']
 __version__ = '0.1.0'

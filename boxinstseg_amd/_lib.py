@@ -321,6 +321,21 @@ FAMILIES = [
     ('attn', ('include/boxinst/boxinst_hip_attn.h',), ATTN_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_inst.h (Box2Mask at test time: query x class top-k, final masks with mask score, area and box)
+INST_TOPK_MAX = 16384
+INST_SIGNATURES = {
+    'bxi_inst_topk_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bxi_inst_paste_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_inst_paste_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+# the families that arrived after tests/test_abi_families.py pinned FAMILIES to its twelve names: the same triples, applied by load()
+# behind FAMILIES with the same check across both lists; tests/test_abi_family_inst.py holds them against headers, exports and guards.
+LATE_FAMILIES = [
+    ('inst', ('include/boxinst/boxinst_hip_inst.h',), INST_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -342,7 +357,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -18,7 +18,9 @@
 //      addresses; byte stores at a misaligned row start and at the row's tail).
 // No global atomics; every output byte is written exactly once.  LDS: rows_cap x (kw + w) floats, rows_cap = the most source rows a band
 // of the launch needs (the host walks the same index arithmetic), kw = the chunk width rounded up to 16; with STATS, three ints per row of
-// the band behind them: the count and the first / last set column of the row inside the chunk (LDS integer atomics: order-free).
+// the band behind them: the count and the first / last set column of the row inside the chunk (LDS integer atomics: order-free); with
+// SCORE (inst_post.hip: Box2Mask), one float per row and 16-byte segment of the chunk behind those: the segment's sum of sigmoid(p) over
+// its set pixels, which one thread per row adds up in ascending order (no float atomics: the order is part of the result).
 #pragma once
 
 #include "common.hpp"
@@ -75,18 +77,19 @@ inline int band_rows_needed(int band_rows, int crop, int out, float scale2, cons
 
 struct RowTab { int r[4]; float H0, H1, h0a, h1a, h0b, h1b; };
 
-inline size_t paste_lds_bytes(int rows_cap, int w, int kw, int band_rows, bool stats) {
-    return sizeof(float) * (size_t)rows_cap * (size_t)(w + kw) + (sizeof(RowTab) + (stats ? 3 * sizeof(int) : 0)) * (size_t)band_rows;
+inline size_t paste_lds_bytes(int rows_cap, int w, int kw, int band_rows, bool stats, bool score = false) {
+    return sizeof(float) * (size_t)rows_cap * (size_t)(w + kw) +
+           (sizeof(RowTab) + (stats ? 3 * sizeof(int) : 0) + (score ? sizeof(float) * (size_t)(kw >> 4) : 0)) * (size_t)band_rows;
 }
 
 // The band height: the largest (16, 8, ..., 1) whose staged rows fit -- `needed(band_rows)` is the most rows a band of the launch reads,
 // plus two rows of margin.  False when even single rows do not fit (source rows wider than ~5000 columns).
 template <class Needed>
-inline bool choose_band(int h, int w, int kw, bool stats, Needed needed, int& band_rows, int& rows_cap, size_t& lds) {
+inline bool choose_band(int h, int w, int kw, bool stats, Needed needed, int& band_rows, int& rows_cap, size_t& lds, bool score = false) {
     for (band_rows = kBandRows; band_rows >= 1; band_rows /= 2) {
         const int cap = needed(band_rows);
         rows_cap = cap + 2 < h ? cap + 2 : h;
-        lds = paste_lds_bytes(rows_cap, w, kw, band_rows, stats);
+        lds = paste_lds_bytes(rows_cap, w, kw, band_rows, stats, score);
         if (lds <= kPasteLdsMax) return true;
     }
     return false;
@@ -102,8 +105,11 @@ struct PasteTile {
 };
 
 // SIGMOID: the source holds logits.  STATS: rows[y * rows_stride], y < Y1 - Y0, = (set bytes, first set column, last set column, 0) of every row of the tile
-// (-1 columns for an empty row) by plain stores, and `valid == false` writes an all-zero tile and reads nothing of `plane`.
-template <bool SIGMOID, bool STATS, class Axis>
+// (-1 columns for an empty row) by plain stores, and `valid == false` writes an all-zero tile and reads nothing of `plane`.  SCORE (with
+// STATS; the source holds logits that are thresholded as they are): the fourth word of the row's record is the bits of the fp32 sum of
+// 1 / (1 + expf(-p)) over the row's set pixels inside the chunk -- every thread adds its 16 pixels in element order, one thread per row
+// adds the row's segments in ascending order.
+template <bool SIGMOID, bool STATS, bool SCORE = false, class Axis>
 __device__ __forceinline__ void paste_tile(float* lds, const PasteTile& t, const Axis& s1h, const Axis& s1w, bool valid, int4* rows,
                                            int rows_stride) {
     const int w = t.w, kw = t.kw, Y0 = t.Y0, Y1 = t.Y1, X0 = t.X0, cw = t.cw;
@@ -118,6 +124,7 @@ __device__ __forceinline__ void paste_tile(float* lds, const PasteTile& t, const
     float* P = lds + (size_t)t.rows_cap * kw;                // [rows_cap][w]
     RowTab* rt = reinterpret_cast<RowTab*>(P + (size_t)t.rows_cap * w);    // [band_rows]
     int* rs = reinterpret_cast<int*>(rt + (Y1 - Y0));        // STATS: [Y1 - Y0][3]
+    float* sg = reinterpret_cast<float*>(rs + 3 * (Y1 - Y0)); // SCORE: [Y1 - Y0][kw / 16]
 
     // a. the band's source rows (kLoadBatch loads in flight per thread before the first is used), the per-row taps
     if (valid) {
@@ -172,6 +179,7 @@ __device__ __forceinline__ void paste_tile(float* lds, const PasteTile& t, const
     for (int it = threadIdx.x; it < items; it += kPasteThreads) {
         const int y = it / segs, x = (it - y * segs) << 4;
         uint32_t word[4] = {0u, 0u, 0u, 0u};
+        float seg_sum = 0.f;                                 // SCORE only
         if (valid) {
             const RowTab r = rt[y];
             const float4* k0 = reinterpret_cast<const float4*>(K + (size_t)r.r[0] * kw + x);
@@ -188,10 +196,14 @@ __device__ __forceinline__ void paste_tile(float* lds, const PasteTile& t, const
                 for (int e = 0; e < 4; ++e) {
                     const float p = r.H0 * (r.h0a * e0[e] + r.h1a * e1[e]) + r.H1 * (r.h0b * e2[e] + r.h1b * e3[e]);
                     wd |= (p > thr ? 1u : 0u) << (8 * e);
+                    if (SCORE) {
+                        if (p > thr && x + 4 * q + e < cw) seg_sum += 1.f / (1.f + expf(-p));
+                    }
                 }
                 word[q] = wd;
             }
         }
+        if (SCORE) sg[y * (kw >> 4) + (x >> 4)] = seg_sum;
         uint8_t* dst = base + (size_t)(Y0 + y) * out_w + X0 + x;
         const int n = cw - x < 16 ? cw - x : 16;
         if (n == 16 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
@@ -224,7 +236,13 @@ __device__ __forceinline__ void paste_tile(float* lds, const PasteTile& t, const
         __syncthreads();
         for (int y = threadIdx.x; y < Y1 - Y0; y += kPasteThreads) {
             const int c = rs[3 * y];
-            rows[(size_t)y * rows_stride] = make_int4(c, c ? rs[3 * y + 1] : -1, rs[3 * y + 2], 0);
+            int fourth = 0;
+            if (SCORE) {
+                float row_sum = 0.f;
+                for (int sgm = 0; sgm < segs; ++sgm) row_sum += sg[y * (kw >> 4) + sgm];
+                fourth = __float_as_int(row_sum);
+            }
+            rows[(size_t)y * rows_stride] = make_int4(c, c ? rs[3 * y + 1] : -1, rs[3 * y + 2], fourth);
         }
     }
 }

@@ -1,0 +1,516 @@
+"""GPU: Box2Mask's test-time path (csrc/inst_post.hip through boxinstseg_amd/inst_post.py) against the float64 restatement of
+tests/inst_post_ref.py and the reference fixture tests/golden/box2mask_test.npz.
+
+Rules (conditions on the inputs, asserted at the top of each test, not measurements):
+* mask bits may differ from ``p64 > 0`` only where |p64| <= 2^-20 x the largest |logit| of the source plane, and at most 0.1 % of a
+  case's pixels lie inside that band; the exact cases have no band at all;
+* the top-k: every index with s64 > cut (1 + 2^-20) is selected, none with s64 < cut (1 - 2^-20), cut = the k-th largest float64 score;
+  the band around the cut holds at most two indices beyond the planted ties;
+* scores are within max(4 |ref32 - ref64|, 4 x 2^-24 |ref64|) (class scores) and max(4 |ref32 - ref64|, 8 x 2^-24 |ref64|) (mask and det
+  scores), ref32 being the reference's own fp32 arithmetic on the CPU;
+* statistics and box corners are exactly what numpy counts on OUR mask bytes."""
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from tests import inst_post_ref as R
+from tests import seg_paste_ref as S
+
+pytestmark = pytest.mark.gpu
+EPS24 = 2.0 ** -24
+
+
+def _t(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+
+def paste(dev, logits, query, cls_scores, up, crop, out):
+    """The entry point on plain tensors -> numpy (masks uint8, stats, mask_scores, boxes)."""
+    from boxinstseg_amd import _lib
+    lib = _lib.load()
+    lg, qu, cs = _t(np.asarray(logits, np.float32), dev), _t(np.asarray(query, np.int64), dev), _t(np.asarray(cls_scores, np.float32), dev)
+    n = len(query)
+    masks = torch.empty((n, *out), dtype=torch.uint8, device=dev)
+    stats = torch.empty((n, 5), dtype=torch.int32, device=dev)
+    ms = torch.empty((n,), dtype=torch.float32, device=dev)
+    boxes = torch.empty((n, 5), dtype=torch.float32, device=dev)
+    nbytes = lib.bxi_inst_paste_workspace_bytes(n, *out)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rc = lib.bxi_inst_paste_u8(lg.data_ptr(), lg.shape[0], lg.shape[1], lg.shape[2], qu.data_ptr(), cs.data_ptr(), n, up[0], up[1], crop[0], crop[1],
+                               out[0], out[1], masks.data_ptr(), stats.data_ptr(), ms.data_ptr(), boxes.data_ptr(), ws.data_ptr(), nbytes,
+                               torch.cuda.current_stream(dev).cuda_stream)
+    assert rc == 0, _lib.STATUS.get(rc, rc)
+    torch.cuda.synchronize()
+    return masks.cpu().numpy(), stats.cpu().numpy(), ms.cpu().numpy(), boxes.cpu().numpy()
+
+
+def ref32_scores(logits, query, cls_scores, up, crop, out):
+    """The reference's fp32 statements on the CPU (box2mask_head.py:453-457, maskformer_fusion_head.py:212-221 and :153-157), restated in
+    torch: (mask, mask_scores, det_scores)."""
+    x = torch.from_numpy(np.asarray(logits, np.float32))[np.asarray(query)][None]
+    x = F.interpolate(x, size=tuple(up), mode='bilinear', align_corners=False)[0][:, :crop[0], :crop[1]]
+    if tuple(out) != tuple(crop):
+        x = F.interpolate(x[:, None], size=tuple(out), mode='bilinear', align_corners=False)[:, 0]
+    b = (x > 0).float()
+    ms = (x.sigmoid() * b).flatten(1).sum(1) / (b.flatten(1).sum(1) + 1e-6)
+    return b.numpy().astype(np.uint8), ms.numpy(), (torch.from_numpy(np.asarray(cls_scores, np.float32)) * ms).numpy()
+
+
+def scores_on(mask, p, cls_scores):
+    """The float64 mask and det scores of given mask bytes on float64 p."""
+    m = mask.astype(bool)
+    with np.errstate(over='ignore', invalid='ignore'):
+        sig = np.where(m, 1.0 / (1.0 + np.exp(-np.where(m, p, 0.0))), 0.0)
+    ms = sig.reshape(len(m), -1).sum(1) / (m.reshape(len(m), -1).sum(1) + 1e-6)
+    return ms, np.asarray(cls_scores, np.float64) * ms
+
+
+def check_counts_and_scores(what, masks, stats, ms, boxes, p, cls_scores, ref32=None, ref64_masks=None):
+    """stats and box corners = numpy on our bytes; mask and det scores within the stated bound of the float64 scores of our bytes.
+    `ref32` = (mask, mask_scores, det_scores) of the reference's fp32 arithmetic: its distance to float64 widens the bound on the rows
+    where all three masks agree."""
+    want = S.stats_of(masks)
+    assert np.array_equal(stats, want), what
+    corners = np.where(want[:, :1] > 0, want[:, 1:] + np.array([0, 0, 1, 1]), 0).astype(np.float32)
+    assert np.array_equal(boxes[:, :4], corners), what
+    ms64, det64 = scores_on(masks, p, cls_scores)
+    tol_m, tol_d = 8 * EPS24 * np.abs(ms64), 8 * EPS24 * np.abs(det64)
+    if ref32 is not None:
+        same = (masks == ref32[0]).reshape(len(masks), -1).all(1) & (masks == ref64_masks).reshape(len(masks), -1).all(1)
+        tol_m = np.where(same, np.maximum(tol_m, 4 * np.abs(ref32[1] - ms64)), tol_m)
+        tol_d = np.where(same, np.maximum(tol_d, 4 * np.abs(ref32[2] - det64)), tol_d)
+    err_m, err_d = np.abs(ms.astype(np.float64) - ms64), np.abs(boxes[:, 4].astype(np.float64) - det64)
+    print(f'{what}: mask score err / bound max {np.max(err_m / np.maximum(tol_m, 1e-300)):.3f}, det {np.max(err_d / np.maximum(tol_d, 1e-300)):.3f}')
+    assert np.all(err_m <= tol_m), (what, err_m, tol_m)
+    assert np.all(err_d <= tol_d), (what, err_d, tol_d)
+
+
+# ---- exact cases -----------------------------------------------------------------------------------------------------------------------
+
+def test_exact_integer_logits(dev):
+    """Integer logits in [-8, 8], up = 4 x the source, identity stage 2: every tap weight is a multiple of 1/8, p is exact in fp32 in any
+    grouping, so masks, statistics and box corners equal the restatement byte for byte (the scores, which hold a sigmoid, by their bound).
+    Plane 4 is all zero (empty mask, zero box, det score 0), plane 5 all +30 (full mask, box (0, 0, W, H), mask score fp32 1.0)."""
+    rng = np.random.default_rng(5)
+    hw, up, crop = (13, 21), (52, 84), (50, 81)
+    logits = rng.integers(-8, 9, (6, *hw)).astype(np.float32)
+    logits[4], logits[5] = 0, 30
+    query, cls = np.arange(6), np.linspace(0.9, 0.4, 6).astype(np.float32)
+    p = R.p64(logits, query, up, crop, crop)
+    assert np.array_equal(p, R.p64_torch(logits, query, up, crop, crop)) and np.array_equal(p, p.astype(np.float32))     # exact: no band
+    assert np.array_equal(p * 64, np.round(p * 64)) and (p[:4] == 0).any()
+    m64, stats64, ms64, boxes64 = R.instance_ref(p, cls)
+    masks, stats, ms, boxes = paste(dev, logits, query, cls, up, crop, crop)
+    assert np.array_equal(masks, m64) and np.array_equal(stats, stats64) and masks.dtype == np.uint8
+    assert np.array_equal(boxes[:, :4], boxes64[:, :4].astype(np.float32)) and boxes.dtype == np.float32
+    check_counts_and_scores('exact', masks, stats, ms, boxes, p, cls, ref32_scores(logits, query, cls, up, crop, crop), m64)
+    assert 0 < stats[0, 0] < crop[0] * crop[1]
+    assert stats[4].tolist() == [0, -1, -1, -1, -1] and boxes[4].tolist() == [0, 0, 0, 0, 0] and ms[4] == 0 and not masks[4].any()
+    assert stats[5].tolist() == [crop[0] * crop[1], 0, 0, crop[1] - 1, crop[0] - 1] and masks[5].all()
+    assert boxes[5, :4].tolist() == [0, 0, crop[1], crop[0]] and ms[5] == np.float32(1.0) and boxes[5, 4] == cls[5]
+    assert 1 - ms64[5] < 1e-9
+
+
+# ---- top-k -----------------------------------------------------------------------------------------------------------------------------
+
+def planted_cls(B, Q, C, k, seed):
+    """Class logits [B,Q,C+1]; in every image two queries carry identical rows such that, in the defined order, one tied pair straddles the
+    cut (ranks k - 1 and k) when k < Q * C, or simply exists when k = Q * C.  Returns (cls, [(lower flat, higher flat) per image])."""
+    out, pairs = [], []
+    def plant(base, qa, qb):
+        cls = base.copy()
+        cls[qb] = cls[qa]
+        order = R.defined_order(R.softmax64(cls).reshape(-1))
+        if k < Q * C:
+            lo, hi = int(order[k - 1]), int(order[k])
+        else:
+            lo, hi = next((int(a), int(c)) for a, c in zip(order, order[1:]) if a // C == qa and c // C == qb and a % C == c % C)
+        return (cls, (lo, hi)) if lo // C == qa and hi // C == qb and lo % C == hi % C else None
+
+    for b in range(B):
+        base = np.random.default_rng(seed + 1000 * b).normal(0, 2.0, (Q, C + 1)).astype(np.float32)
+        found = next((f for qa in range(Q - 1) for qb in (qa + 1, Q - 1) for f in [plant(base, qa, qb)] if f), None)
+        assert found, 'no planted tie found'
+        out.append(found[0])
+        pairs.append(found[1])
+    return np.stack(out), pairs
+
+
+@pytest.mark.parametrize('B,Q,things,stuff,k', [(2, 100, 80, 0, 100), (1, 7, 3, 0, 21), (2, 100, 60, 20, 100), (1, 7, 2, 1, 21)],
+                         ids=['coco', 'all', 'coco_stuff', 'all_stuff'])
+def test_topk(dev, B, Q, things, stuff, k):
+    from boxinstseg_amd import instance_topk
+    C = things + stuff
+    cls, pairs = planted_cls(B, Q, C, k, 17)
+    s64 = R.softmax64(cls).reshape(B, -1)
+    ref32 = torch.softmax(torch.from_numpy(cls), -1)[..., :-1].reshape(B, -1).numpy()
+    scores, labels, query, count = (x.cpu().numpy() for x in instance_topk(_t(cls, dev), things, stuff, k))
+    assert scores.shape == labels.shape == query.shape == (B, k) and count.shape == (B,) and count.dtype == np.int32
+    assert scores.dtype == np.float32 and labels.dtype == np.int64 and query.dtype == np.int64
+    for b in range(B):
+        order = R.defined_order(s64[b])
+        cut = s64[b][order[k - 1]]
+        tied = set(pairs[b])
+        band = [i for i in range(Q * C) if cut * (1 - 2.0 ** -20) <= s64[b][i] <= cut * (1 + 2.0 ** -20)]
+        if k < Q * C:
+            assert s64[b][pairs[b][0]] == s64[b][pairs[b][1]] == cut and len(set(band) - tied) <= 2       # the input condition
+        n = int(count[b])
+        flat = query[b, :n] * C + labels[b, :n]
+        # the things filter and the rows behind the count
+        assert np.all(labels[b, :n] < things) and np.all(labels[b, :n] >= 0) and np.all((query[b, :n] >= 0) & (query[b, :n] < Q))
+        assert labels[b, n:].tolist() == [-1] * (k - n) and query[b, n:].tolist() == [-1] * (k - n) and scores[b, n:].tolist() == [0.0] * (k - n)
+        assert len(set(flat.tolist())) == n
+        # the selection: everything above the band, nothing below it, the planted pair by the rule (lower flat index first)
+        is_thing = (np.arange(Q * C) % C) < things
+        must = {int(i) for i in np.nonzero((s64[b] > cut * (1 + 2.0 ** -20)) & is_thing)[0]}
+        never = {int(i) for i in np.nonzero(s64[b] < cut * (1 - 2.0 ** -20))[0]}
+        got = set(flat.tolist())
+        assert must <= got and not (got & never)
+        n_sel = n + int((~is_thing[order[:k]]).sum()) if len(set(band) - tied) == 0 else None
+        if k < Q * C:
+            lo, hi = pairs[b]
+            assert hi not in got and (lo in got) == bool(is_thing[lo])
+        else:
+            assert n == int(is_thing.sum()) and got == {int(i) for i in np.nonzero(is_thing)[0]}
+            lo, hi = pairs[b]
+            if is_thing[lo]:
+                at = flat.tolist()
+                assert at.index(lo) + 1 == at.index(hi) and scores[b, at.index(lo)] == scores[b, at.index(hi)]
+        if n_sel is not None:
+            assert n_sel == k
+        # the order: descending in OUR scores, equal scores by ascending flat index
+        sc = scores[b, :n]
+        assert np.all(sc[:-1] >= sc[1:]) and np.all((sc[:-1] > sc[1:]) | (flat[:-1] < flat[1:]))
+        # the scores
+        tol = np.maximum(4 * np.abs(ref32[b][flat].astype(np.float64) - s64[b][flat]), 4 * EPS24 * s64[b][flat])
+        err = np.abs(sc.astype(np.float64) - s64[b][flat])
+        print(f'topk B{b}: count {n}, score err / bound max {np.max(err / tol):.3f}')
+        assert np.all(err <= tol), (err / tol).max()
+        if stuff:
+            assert 0 < n < k or k == Q * C
+
+
+def test_topk_nan_row_and_2d_input(dev):
+    """A query row with a NaN gives NaN scores, which order after every number: selected last (k = Q * C), with their labels and NaN scores;
+    never selected when k leaves them out.  A [Q,C+1] input returns results without the batch axis."""
+    from boxinstseg_amd import instance_topk
+    Q, C = 7, 3
+    cls = np.random.default_rng(2).normal(0, 2, (Q, C + 1)).astype(np.float32)
+    cls[3, 1] = np.nan
+    s, lab, q, n = (x.cpu().numpy() for x in instance_topk(_t(cls, dev), C, 0, Q * C))
+    assert s.shape == (Q * C,) and n.shape == () and int(n) == Q * C
+    flat = q * C + lab
+    assert flat[-C:].tolist() == [9, 10, 11] and np.isnan(s[-C:]).all() and not np.isnan(s[:-C]).any()
+    want = R.topk_ref(cls, C, Q * C)[3]
+    assert np.array_equal(flat, want)
+    s2, lab2, q2, n2 = (x.cpu().numpy() for x in instance_topk(_t(cls[None], dev), C, 0, Q * C - C))
+    assert s2.shape == (1, Q * C - C) and int(n2[0]) == Q * C - C and np.array_equal(q2[0] * C + lab2[0], flat[:-C]) and np.array_equal(s2[0], s[:-C])
+
+
+# ---- masks -----------------------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope='module')
+def golden():
+    with np.load(R.GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _meta(c):
+    return dict(batch_input_shape=tuple(c['up']), img_shape=(*c['crop'], 3), ori_shape=(*c['ori'], 3))
+
+
+@pytest.mark.parametrize('resized', [False, True], ids=['raw', 'resized'])
+@pytest.mark.parametrize('name', sorted(R.CASES))
+def test_reference_fixture(dev, golden, name, resized):
+    """box2mask_instances on the fixture's inputs against the reference's recorded results and the float64 restatement.  `resized`: the
+    mask logits arrive at batch_input_shape already, as the reference head returns them (stage 1 is the identity; the resize itself is
+    torch's, on the CPU)."""
+    import boxinstseg_amd as B
+    c = R.CASES[name]
+    g = {k.split('/', 1)[1]: v for k, v in golden.items() if k.startswith(name + '/')}
+    cls, pred = g['cls'], g['pred']
+    C, out = c['things'] + c['stuff'], tuple(c['ori']) if c['rescale'] else tuple(c['crop'])
+    src = pred
+    if resized:
+        src = F.interpolate(torch.from_numpy(pred)[None], size=tuple(c['up']), mode='bilinear', align_corners=False)[0].numpy()
+    scores64, labels64, query64, flat64 = R.topk_ref(cls, c['things'], c['k'])
+    p = R.p64(src, query64, c['up'], c['crop'], out)
+    assert R.band_share(p, src, query64) <= R.BAND_SHARE                        # the input condition
+    res = B.box2mask_instances(_t(cls[None], dev), _t(src[None], dev), [_meta(c)], dict(max_per_image=c['k']), c['things'], c['stuff'],
+                               rescale=c['rescale'])
+    assert len(res) == 1
+    r = res[0]
+    n = int(r.count)
+    assert n == len(flat64) and (n < c['k']) == (c['stuff'] > 0) and tuple(r.masks.shape) == (c['k'], *out) and r.masks.dtype == torch.bool
+    labels, query = r.labels.cpu().numpy(), r.query.cpu().numpy()
+    assert np.array_equal(query[:n] * C + labels[:n], flat64) and np.array_equal(labels[:n], labels64)          # distinct scores: one order
+    assert labels[n:].tolist() == [-1] * (c['k'] - n)
+    masks, stats = r.masks.view(torch.uint8).cpu().numpy(), r.mask_stats.cpu().numpy()
+    ms, boxes, cls_scores = r.mask_scores.cpu().numpy(), r.bboxes.cpu().numpy(), r.scores.cpu().numpy()
+    R.check_masks(masks[:n], p, src, query64, name)
+    if not resized:
+        pt = R.p64_torch(src, query64, c['up'], c['crop'], out)
+        R.check_masks(masks[:n], pt, src, query64, name + ' vs F.interpolate in float64', widen=np.abs(p - pt))
+    # the reference's rows, in our order; its bits may differ from ours only inside the band
+    order = np.array([g['flat'].tolist().index(f) for f in flat64], np.int64)
+    ref_masks = np.unpackbits(g['masks'], axis=1)[:, :out[0] * out[1]].reshape(-1, *out)[order]
+    tau = R.tie_band(src, query64)[:, None, None]
+    assert np.array_equal(g['labels'][order], labels[:n])
+    if not resized:
+        assert not ((masks[:n] != ref_masks) & (np.abs(p) > tau)).any()
+        ref32 = (ref_masks, g['mask_scores'][order], g['bboxes'][order, 4])
+    else:
+        ref32 = None
+    check_counts_and_scores(name, masks[:n], stats[:n], ms[:n], boxes[:n], p, cls_scores[:n], ref32, (p > 0).astype(np.uint8))
+    tol = np.maximum(4 * np.abs(g['cls_scores'][order].astype(np.float64) - scores64), 4 * EPS24 * scores64)
+    assert np.all(np.abs(cls_scores[:n] - scores64) <= tol)
+    # rows behind the count: empty masks, empty statistics, zero boxes
+    assert not masks[n:].any() and np.all(stats[n:] == np.array([0, -1, -1, -1, -1])) and not boxes[n:].any() and not ms[n:].any()
+    if name == 'zero_plane':
+        z = int(np.nonzero(query64 == 2)[0][0])
+        assert not masks[z].any() and boxes[z].tolist() == [0, 0, 0, 0, 0] and stats[z].tolist() == [0, -1, -1, -1, -1]
+
+
+def _blobs(rng, n, h, w):
+    yy, xx = np.mgrid[0:h, 0:w]
+    cy, cx = rng.uniform(0.2 * h, 0.8 * h, n), rng.uniform(0.2 * w, 0.8 * w, n)
+    r = rng.uniform(0.1, 0.35, n) * min(h, w)
+    d = np.sqrt((yy[None] - cy[:, None, None]) ** 2 + (xx[None] - cx[:, None, None]) ** 2)
+    return (0.5 * (r[:, None, None] - d) + rng.normal(0, 0.2, (n, h, w))).astype(np.float32)
+
+
+def test_full_size_and_peak_memory(dev):
+    """The test pipeline's shape: Q = 100, C = 80, prediction 200 x 336, batch_input_shape 800 x 1344, img_shape 800 x 1333, ori_shape
+    480 x 640 with rescale.  The peak device memory above the inputs stays below n (ori_h ori_w + 32) bytes + the queried workspace + 1 MB
+    (the reference's first F.interpolate alone allocates 430 MB), and all 100 masks obey the rules against the float64 restatement."""
+    import boxinstseg_amd as B
+    from boxinstseg_amd import _lib
+    rng = np.random.default_rng(3)
+    Q, C, hw, up, crop, out = 100, 80, (200, 336), (800, 1344), (800, 1333), (480, 640)
+    pred = _blobs(rng, Q, *hw)
+    cls = rng.normal(0, 2.0, (Q, C + 1)).astype(np.float32)
+    meta = dict(batch_input_shape=up, img_shape=(*crop, 3), ori_shape=(*out, 3))
+    cfg = dict(max_per_image=100)
+    d_cls, d_pred = _t(cls[None], dev), _t(pred[None], dev)
+    B.box2mask_instances(d_cls[:, :4], d_pred[:, :4, :8, :8], [dict(batch_input_shape=(32, 32), img_shape=(30, 31, 3), ori_shape=(9, 9, 3))],
+                         dict(max_per_image=2), C, 0, rescale=True)               # the library is loaded
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    r = B.box2mask_instances(d_cls, d_pred, [meta], cfg, C, 0, rescale=True)[0]
+    torch.cuda.synchronize()
+    growth = torch.cuda.max_memory_allocated(dev) - base
+    n = 100
+    bound = n * (out[0] * out[1] + 32) + _lib.load().bxi_inst_paste_workspace_bytes(n, *out) + (1 << 20)
+    print(f'peak above the inputs {growth / 1e6:.2f} MB, bound {bound / 1e6:.2f} MB')
+    assert growth < bound, (growth, bound)
+    assert int(r.count) == n and tuple(r.masks.shape) == (n, *out)
+    labels, query = r.labels.cpu().numpy(), r.query.cpu().numpy()
+    flat64 = R.topk_ref(cls, C, n)[3]
+    assert sorted((query * C + labels).tolist()) == sorted(flat64.tolist())
+    masks, stats = r.masks.view(torch.uint8).cpu().numpy(), r.mask_stats.cpu().numpy()
+    ms, boxes, cls_scores = r.mask_scores.cpu().numpy(), r.bboxes.cpu().numpy(), r.scores.cpu().numpy()
+    assert np.array_equal(stats, S.stats_of(masks)) and (stats[:, 0] > 0).all()
+    inside = total = 0
+    for lo in range(0, n, 20):
+        sl = slice(lo, lo + 20)
+        p = R.p64(pred, query[sl], up, crop, out)
+        tau = R.tie_band(pred, query[sl])[:, None, None]
+        inside, total = inside + int((np.abs(p) <= tau).sum()), total + p.size
+        bad = (masks[sl] != (p > 0)) & (np.abs(p) > tau)
+        assert not bad.any(), (lo, int(bad.sum()))
+        check_counts_and_scores(f'full size {lo}', masks[sl], stats[sl], ms[sl], boxes[sl], p, cls_scores[sl])
+    assert inside <= R.BAND_SHARE * total
+
+
+def test_permutation_repeats_and_bad_indices(dev):
+    c = R.CASES['rescale']
+    pred = R.case_inputs('rescale')[1]
+    out = tuple(c['ori'])
+    base = paste(dev, pred, np.arange(12), np.full(12, 0.5, np.float32), c['up'], c['crop'], out)
+    query = np.array([7, 3, 3, -1, 11, 12, 0, 1 << 40, 7, -(1 << 40)])
+    cls = np.linspace(0.1, 1.0, len(query)).astype(np.float32)
+    masks, stats, ms, boxes = paste(dev, pred, query, cls, c['up'], c['crop'], out)
+    for i, q in enumerate(query):
+        if 0 <= q < 12:
+            assert np.array_equal(masks[i], base[0][q]) and np.array_equal(stats[i], base[1][q]) and ms[i] == base[2][q]
+            assert np.array_equal(boxes[i, :4], base[3][q, :4]) and boxes[i, 4] == np.float32(cls[i]) * ms[i]
+        else:
+            assert not masks[i].any() and stats[i].tolist() == [0, -1, -1, -1, -1] and ms[i] == 0 and boxes[i].tolist() == [0, 0, 0, 0, 0]
+    assert base[1][:, 0].min() > 0
+
+
+def test_nan_plane_gives_zeros(dev):
+    c = R.CASES['rescale']
+    pred = R.case_inputs('rescale')[1].copy()
+    clean = paste(dev, pred, [0, 1, 2], [0.5, 0.5, 0.5], c['up'], c['crop'], tuple(c['ori']))
+    pred[1] = np.nan
+    pred[2, 4, 5] = np.nan
+    masks, stats, ms, boxes = paste(dev, pred, [0, 1, 2], [0.5, 0.5, 0.5], c['up'], c['crop'], tuple(c['ori']))
+    assert np.array_equal(masks[0], clean[0][0]) and ms[0] == clean[2][0]
+    assert not masks[1].any() and stats[1].tolist() == [0, -1, -1, -1, -1] and ms[1] == 0 and boxes[1].tolist() == [0, 0, 0, 0, 0]
+    assert np.isfinite(ms[2]) and 0 < stats[2, 0] <= clean[1][2, 0] and not (masks[2] & ~clean[0][2]).any()      # NaN pixels compare false
+
+
+def test_two_calls_are_bit_identical(dev):
+    import boxinstseg_amd as B
+    c = R.CASES['stuff']
+    cls, pred = R.case_inputs('stuff')
+    d_cls, d_pred = _t(np.stack([cls, cls[::-1]]), dev), _t(np.stack([pred, pred]), dev)       # other pairs of class row and plane
+    runs = []
+    for _ in range(2):
+        res = B.box2mask_instances(d_cls, d_pred, [_meta(c), _meta(c)], dict(max_per_image=c['k']), c['things'], c['stuff'], rescale=True)
+        runs.append([r.host_block.clone() for r in res])
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(*runs)) and not torch.equal(runs[0][0], runs[0][1])
+
+
+def test_batch_equals_the_per_image_loop(dev):
+    import boxinstseg_amd as B
+    c = R.CASES['stuff']
+    cls, pred = R.case_inputs('stuff')
+    d_cls, d_pred = _t(np.stack([cls, cls[::-1] * 0.5]), dev), _t(np.stack([pred, pred[::-1]]), dev)
+    metas = [_meta(c), dict(batch_input_shape=tuple(c['up']), img_shape=(47, 80, 3), ori_shape=(31, 50, 3))]
+    cfg = dict(max_per_image=c['k'])
+    for rescale in (True, False):
+        got = B.box2mask_instances(d_cls, d_pred, metas, cfg, c['things'], c['stuff'], rescale=rescale)
+        assert [tuple(r.masks.shape[1:]) for r in got] == ([(64, 100), (31, 50)] if rescale else [(52, 84), (47, 80)])
+        for b, r in enumerate(got):
+            one = B.box2mask_instances(d_cls[b:b + 1], d_pred[b:b + 1], [dict(metas[b])], cfg, c['things'], c['stuff'], rescale=rescale)[0]
+            assert torch.equal(r.host_block, one.host_block) and int(r.count) == int(one.count) > 0
+            for key in ('labels', 'bboxes', 'masks', 'mask_stats', 'mask_scores', 'scores', 'query'):
+                assert torch.equal(getattr(r, key), getattr(one, key)), (b, key)
+            # the views are the buffer
+            assert r.labels.data_ptr() == r.host_block.data_ptr() and r.masks.dtype == torch.bool
+    head = B.MaskFormerFusionHead(c['things'], c['stuff'], test_cfg=dict(panoptic_on=False, instance_on=True, max_per_image=c['k']))
+    out = head.simple_test(d_cls, d_pred, metas, rescale=True)
+    got = B.box2mask_instances(d_cls, d_pred, metas, cfg, c['things'], c['stuff'], rescale=True)
+    for o, r in zip(out, got):
+        labels, bboxes, masks = o['ins_results']
+        n = int(r.count)
+        assert list(o) == ['ins_results'] and len(labels) == n < c['k']         # stuff classes: the rows are cut at the count
+        assert torch.equal(labels, r.labels[:n]) and torch.equal(bboxes, r.bboxes[:n]) and torch.equal(masks, r.masks[:n])
+    things_only = B.MaskFormerFusionHead(c['things'] + c['stuff'], 0, test_cfg=dict(panoptic_on=False, instance_on=True, max_per_image=c['k']))
+    labels, bboxes, masks = things_only.simple_test(d_cls, d_pred, metas)[0]['ins_results']
+    assert len(labels) == c['k'] and tuple(masks.shape) == (c['k'], 52, 84) and tuple(bboxes.shape) == (c['k'], 5)
+
+
+# ---- formatting ------------------------------------------------------------------------------------------------------------------------
+
+def _fixture_results(dev, name='stuff'):
+    import boxinstseg_amd as B
+    c = R.CASES[name]
+    cls, pred = R.case_inputs(name)
+    return c, B.box2mask_instances(_t(cls[None], dev), _t(pred[None], dev), [_meta(c)], dict(max_per_image=c['k']), c['things'], c['stuff'],
+                                   rescale=c['rescale'])[0]
+
+
+@pytest.mark.parametrize('name', ['stuff', 'zero_plane'])
+def test_format_results_against_the_restated_loop(dev, name):
+    """maskformer.py:155-175 restated (tests/inst_post_ref.py: format_ref, held against the reference's own loop by the fixture) on our
+    results: all `count` detections are kept, the empty mask of 'zero_plane' included."""
+    from boxinstseg_amd import box2mask_format_results
+    c, r = _fixture_results(dev, name)
+    n = int(r.count)
+    boxes, masks = box2mask_format_results(r, c['things'])
+    wb, wm = R.format_ref(r.labels[:n].cpu().numpy(), r.bboxes[:n].cpu().numpy(), r.masks[:n].cpu().numpy(), c['things'])
+    assert len(boxes) == len(masks) == c['things'] and sum(len(m) for m in masks) == n
+    for a, b in zip(boxes, wb):
+        assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.shape == b.shape and np.array_equal(a, b)
+    for per, want in zip(masks, wm):
+        assert len(per) == len(want)
+        for a, b in zip(per, want):
+            assert isinstance(a, np.ndarray) and a.dtype == np.bool_ and np.array_equal(a, b)
+    if name == 'zero_plane':
+        assert any(not m.any() for per in masks for m in per)                  # the empty mask is kept, as the reference keeps it
+
+
+def test_format_results_is_one_copy_and_one_sync(dev, monkeypatch):
+    from boxinstseg_amd import box2mask_format_results
+    c, r = _fixture_results(dev)
+    torch.cuda.synchronize()
+    calls = dict(sync=0, d2h=0)
+    real_sync, real_copy = torch.cuda.Stream.synchronize, torch.Tensor.copy_
+
+    def sync(self):
+        calls['sync'] += 1
+        return real_sync(self)
+
+    def copy_(self, src, *a, **k):
+        if not self.is_cuda and src.is_cuda:
+            calls['d2h'] += 1
+            assert self.is_pinned()
+        return real_copy(self, src, *a, **k)
+
+    def refuse(name):
+        real = getattr(torch.Tensor, name)
+
+        def fn(self, *a, **k):
+            assert not self.is_cuda, f'Tensor.{name} on a device tensor: a second copy or synchronisation'
+            return real(self, *a, **k)
+        return fn
+    monkeypatch.setattr(torch.cuda.Stream, 'synchronize', sync)
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: pytest.fail('torch.cuda.synchronize'))
+    monkeypatch.setattr(torch.Tensor, 'copy_', copy_)
+    for name in ('cpu', 'item', 'tolist', 'numpy', 'nonzero'):
+        monkeypatch.setattr(torch.Tensor, name, refuse(name))
+    boxes, masks = box2mask_format_results(r, c['things'])
+    monkeypatch.undo()
+    assert calls == dict(sync=1, d2h=1)
+    flat = [m for per in masks for m in per]
+    assert len(flat) == int(r.count) and all(m.base is not None for m in flat)               # views of the one host buffer
+
+
+# ---- errors ----------------------------------------------------------------------------------------------------------------------------
+
+def test_errors(dev):
+    import boxinstseg_amd as B
+    cls, pred = torch.rand(1, 5, 4, device=dev), torch.rand(1, 5, 7, 9, device=dev)
+    meta = dict(batch_input_shape=(28, 36), img_shape=(27, 33, 3), ori_shape=(40, 51, 3))
+    cfg = dict(max_per_image=4)
+    assert B.box2mask_instances(cls[:0], pred[:0], [], cfg, 3, 0) == []
+    with pytest.raises(RuntimeError, match='CUDA'):
+        B.instance_topk(cls.cpu(), 3, 0, 4)
+    with pytest.raises(RuntimeError, match='CUDA'):
+        B.box2mask_instances(cls, pred.cpu(), [meta], cfg, 3, 0)
+    with pytest.raises(RuntimeError, match='fp32'):
+        B.instance_topk(cls.half(), 3, 0, 4)
+    with pytest.raises(RuntimeError, match='fp32'):
+        B.instance_topk(cls[0, 0], 3, 0, 4)
+    with pytest.raises(RuntimeError, match='columns'):
+        B.instance_topk(cls, 3, 1, 4)
+    with pytest.raises(NotImplementedError, match='boxinst_hip_inst.h'):
+        B.instance_topk(cls, 3, 0, 16)                                         # k > Q * C
+    with pytest.raises(NotImplementedError, match='boxinst_hip_inst.h'):
+        B.instance_topk(torch.rand(1, 130, 131, device=dev), 130, 0, 4)        # Q * C > BXI_INST_TOPK_MAX
+    with pytest.raises(RuntimeError, match='BAD_SHAPE'):
+        B.instance_topk(cls, 3, 0, 0)
+    with pytest.raises(RuntimeError, match='fp32'):
+        B.box2mask_instances(cls.double(), pred, [meta], cfg, 3, 0)
+    with pytest.raises(RuntimeError, match='fp32'):
+        B.box2mask_instances(cls, pred.half(), [meta], cfg, 3, 0)
+    with pytest.raises(RuntimeError, match='fp32'):
+        B.box2mask_instances(cls, pred[0], [meta], cfg, 3, 0)
+    with pytest.raises(RuntimeError, match='do not belong'):
+        B.box2mask_instances(cls, pred[:, :4], [meta], cfg, 3, 0)
+    with pytest.raises(RuntimeError, match='do not belong'):
+        B.box2mask_instances(cls, pred, [meta, meta], cfg, 3, 0)
+    with pytest.raises(RuntimeError, match='larger than batch_input_shape'):
+        B.box2mask_instances(cls, pred, [dict(meta, img_shape=(29, 33, 3))], cfg, 3, 0)
+    with pytest.raises(KeyError):
+        B.box2mask_instances(cls, pred, [dict(img_shape=(27, 33, 3), ori_shape=(40, 51, 3))], cfg, 3, 0)
+    r = B.box2mask_instances(cls, pred, [meta], cfg, 3, 0, rescale=True)[0]
+    assert tuple(r.masks.shape) == (4, 40, 51) and int(r.count) == 4
+    with pytest.raises(RuntimeError, match='host_block'):
+        B.box2mask_format_results(types.SimpleNamespace(masks=r.masks), 3)
+    with pytest.raises(RuntimeError, match='host_block'):
+        B.box2mask_format_results(types.SimpleNamespace(masks=r.masks[:2], host_block=r.host_block), 3)
+    head = B.MaskFormerFusionHead(3, 0, test_cfg=dict(panoptic_on=True, instance_on=True))
+    with pytest.raises(NotImplementedError, match='panoptic_on'):
+        head.simple_test(cls, pred, [meta])
+    head = B.MaskFormerFusionHead(3, 0, test_cfg=dict(panoptic_on=False, semantic_on=True, instance_on=True))
+    with pytest.raises(NotImplementedError, match='semantic_on'):
+        head.simple_test(cls, pred, [meta])
