@@ -38,6 +38,8 @@ Public surface (mirrors the reference's for this path):
     solo_dynamic_masks                 <-> the dynamic 1x1 convolution and sigmoid of DiscoBoxSOLOv2Head.loss / corr_loss (one launch, autograd)
     solo_dynamic_masks_pair            : the same for the student's and the teacher's maps with one grid_order (the teacher without a backward)
     solo_candidate_masks               <-> F.conv2d(seg_preds, kernel_preds[rows]).sigmoid() of get_seg_single, the kernel rows read in place
+      (all three) compute='half'       : the same statements as the reference's autocast runs them -- fp16 / bf16 tensors read in place,
+                                         fp32 accumulation, half masks and gradients (csrc/solo_dconv16.hip); discobox_get_seg_single(conv='hip_half')
     box2mask_attn_mask, attn_mask_bits <-> the attention mask of Box2MaskHead.forward_head and its repair in forward, as bits (PackedAttnMask), one launch
     pack_attn_mask                     : an existing bool attention mask [B*M,Q,S] or [Q,S] packed to a PackedAttnMask on the device
     masked_attention                   : the attention core of torch.nn.MultiheadAttention with that mask, forward and backward, no [Q,S] tensor

@@ -336,6 +336,24 @@ LATE_FAMILIES = [
     ('inst', ('include/boxinst/boxinst_hip_inst.h',), INST_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_dconv16.h (the dynamic mask convolution on fp16 / bf16 tensors read in place, fp32 accumulation on the MFMA)
+DCONV16_F16, DCONV16_BF16, DCONV16_OUT_F32, DCONV16_TILE = 0, 1, 2, 64
+DCONV16_SIGNATURES = {
+    'bxi_solo_dconv16_forward_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_solo_dconv16_forward': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_void_p,
+                                         C.POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_solo_dconv16_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'bxi_solo_dconv16_backward': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_void_p,
+                                          C.POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, C.POINTER(c_void_p), c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
+}
+
+# the half-precision siblings of families above: a third list, because tests/test_abi_family_inst.py pins LATE_FAMILIES to ['inst'];
+# the same triples, applied by load() behind the other two with the same check across all lists (tests/test_abi_family_dconv16.py)
+HALF_FAMILIES = [
+    ('dconv16', ('include/boxinst/boxinst_hip_dconv16.h',), DCONV16_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -357,7 +375,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES + LATE_FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -17,27 +17,13 @@
 //   sits in LDS.  A wave owns blocks of 32 channels: grad_feat's block is A = kernel values [e][i], B = g [i][pixel], k = the image's rows
 //   ascending; grad_kernel's per-tile partial is A = g [i][pixel], B = the feature block [pixel][e] (staged through LDS, read coalesced),
 //   k = the tile's pixels ascending, stored to part[tile][row][e].
-// dconv_reduce_kernel   gk[row][e] = the partials of the row's image's tiles, 32 interleaved sums added in order.
+// dconv_reduce_kernel   (solo_dconv_device.hpp) gk[row][e] = the partials of the row's image's tiles, 32 interleaved sums added in order.
 // dconv_scatter_kernel  every element of every gradient map: the sum of gk over the rows of its segment that name its cell, in row order.
-#include "common.hpp"
-
-#include "../../include/boxinst/boxinst_hip_dconv.h"
+#include "solo_dconv_device.hpp"                     // the table, locate(), acc_row() and the argument checks, shared with solo_dconv16.hip
 
 namespace bxi {
 
-constexpr int kDcThreads = 256;
 constexpr int kDcStride = BXI_DCONV_TILE + 1;        // LDS row stride of the backward's tiles: column reads hit 32 banks
-
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-struct DconvTable {
-    const float* maps[BXI_DCONV_MAX_LEVELS];
-    float* gmaps[BXI_DCONV_MAX_LEVELS];
-    int cells[BXI_DCONV_MAX_LEVELS];                                 // cells of one image's map of the level (S^2), or the matrix's rows
-    int start[BXI_DCONV_MAX_LEVELS * BXI_MAX_IMAGES + 1];            // start[l*B + b]: first row of segment (l, b); start[L*B] = N
-    int chunk0[BXI_MAX_IMAGES + 1];                                  // first chunk of 32 rows of image b in kT; chunk0[B] = all chunks
-    int L, B, layout;
-};
 
 __device__ __forceinline__ f16v mfma32(float a, float b, f16v c) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -51,24 +37,6 @@ __device__ __forceinline__ f16v mfma32(float a, float b, f16v c) {
 __host__ __device__ __forceinline__ int e8_of(int E) { return (E + 7) & ~7; }
 __device__ __forceinline__ size_t kt_at(int E8, int chunk, int e, int r) {
     return (size_t)chunk * E8 * 32 + (size_t)((e >> 3) * 2 + (e & 1)) * 128 + r * 4 + ((e >> 1) & 3);
-}
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
-
-__device__ __forceinline__ int rows_of_image(const DconvTable& t, int b) {
-    int n = 0;
-    for (int l = 0; l < t.L; ++l) n += t.start[l * t.B + b + 1] - t.start[l * t.B + b];
-    return n;
-}
-// the j-th row of image b (levels in order): its output row, or -1 past the image's last; `lev` its level
-__device__ __forceinline__ int locate(const DconvTable& t, int b, int j, int& lev) {
-    int row = -1;
-    lev = 0;
-    for (int l = 0; l < t.L; ++l) {
-        const int s0 = t.start[l * t.B + b], cnt = t.start[l * t.B + b + 1] - s0;
-        if (j >= 0 && j < cnt) { row = s0 + j; lev = l; }
-        j -= cnt;                                                    // negative from the hit on
-    }
-    return row;
 }
 // where kernel(row, e = 0) lies and the stride between channels; nullptr for no row or a cell outside its map (never read)
 __device__ __forceinline__ const float* kernel_of(const DconvTable& t, const int64_t* cells, int b, int row, int lev, int E, int& estride,
@@ -301,24 +269,6 @@ __global__ void __launch_bounds__(kDcThreads) dconv_bwd_kernel(const DconvTable 
     }
 }
 
-// gk[row][e] = sum over the tiles of part[tile][row][e]: kDcReduceLanes interleaved sums (tile % 32), then those in order.
-constexpr int kDcReduceLanes = 32;
-__global__ void __launch_bounds__(32 * kDcReduceLanes) dconv_reduce_kernel(const float* __restrict__ part, float* __restrict__ gk, int E, int tiles,
-                                                                           int N) {
-    __shared__ float red[kDcReduceLanes][32];
-    const int row = blockIdx.x, e = blockIdx.y * 32 + (threadIdx.x & 31), tl = threadIdx.x >> 5;
-    float s = 0.f;
-    if (e < E)
-        for (int k = tl; k < tiles; k += kDcReduceLanes) s += part[((size_t)k * N + row) * E + e];
-    red[tl][threadIdx.x & 31] = s;
-    __syncthreads();
-    if (tl == 0 && e < E) {
-        float v = red[0][threadIdx.x];
-        for (int k = 1; k < kDcReduceLanes; ++k) v += red[k][threadIdx.x];
-        gk[(size_t)row * E + e] = v;
-    }
-}
-
 __global__ void __launch_bounds__(kDcThreads) dconv_scatter_kernel(const DconvTable t, const int64_t* __restrict__ cells,
                                                                    const float* __restrict__ gk, int E) {
     const int l = blockIdx.y, ncell = t.cells[l];
@@ -335,43 +285,6 @@ __global__ void __launch_bounds__(kDcThreads) dconv_scatter_kernel(const DconvTa
     t.gmaps[l][idx] = s;
 }
 
-// the checks both entry points share; fills the table
-static int dconv_table(int B, int E, int H, int W, const void* const* maps, const int* grids, int L, int layout, const int* seg_counts, int N,
-                       int activation, DconvTable& t) {
-    if (!maps || !grids || !seg_counts) return BXI_ERR_NULL_POINTER;
-    if (B < 1 || B > BXI_MAX_IMAGES || L < 1 || L > BXI_DCONV_MAX_LEVELS || E < 1 || E > BXI_DCONV_MAX_E || H < 1 || W < 1 || N < 0)
-        return BXI_ERR_BAD_SHAPE;
-    if (!fits_i32((int64_t)H * W) || !fits_i32((int64_t)B * E * H * W) || !fits_i32((int64_t)N * H * W)) return BXI_ERR_BAD_SHAPE;
-    if (layout != BXI_DCONV_MAPS && layout != BXI_DCONV_ROWS) return BXI_ERR_BAD_ARGUMENT;
-    if (activation != BXI_DCONV_NONE && activation != BXI_DCONV_SIGMOID) return BXI_ERR_BAD_ARGUMENT;
-    if (layout == BXI_DCONV_ROWS && (L != 1 || B != 1)) return BXI_ERR_BAD_SHAPE;
-    t.L = L; t.B = B; t.layout = layout;
-    int64_t at = 0;
-    for (int l = 0; l < L; ++l) {
-        if (grids[l] < 1) return BXI_ERR_BAD_SHAPE;
-        const int64_t ncell = layout == BXI_DCONV_ROWS ? (int64_t)grids[l] : (int64_t)grids[l] * grids[l];
-        if (!fits_i32(ncell) || !fits_i32((int64_t)(layout == BXI_DCONV_ROWS ? 1 : B) * E * ncell)) return BXI_ERR_BAD_SHAPE;
-        t.cells[l] = (int)ncell;
-        t.maps[l] = static_cast<const float*>(maps[l]);
-        t.gmaps[l] = nullptr;
-        for (int b = 0; b < B; ++b) {
-            const int c = seg_counts[l * B + b];
-            if (c < 0 || c > N) return BXI_ERR_BAD_SHAPE;
-            t.start[l * B + b] = (int)at;
-            at += c;
-        }
-    }
-    if (at != N) return BXI_ERR_BAD_SHAPE;
-    t.start[L * B] = N;
-    t.chunk0[0] = 0;
-    for (int b = 0; b < B; ++b) {
-        int nb = 0;
-        for (int l = 0; l < L; ++l) nb += seg_counts[l * B + b];
-        t.chunk0[b + 1] = t.chunk0[b] + (nb + 31) / 32;
-    }
-    return BXI_OK;
-}
-
 // kT [slots][E8][32] with slots = N / 32 + B (never fewer than the chunks: sum_b ceil(n_b / 32)), then for the backward part [tiles][N][E]
 // and gk [N][E], back to back: floats only, kT a multiple of 128 bytes, no padding, so every byte of the workspace is written
 struct DconvSpace { float *kT, *part, *gk; int slots; };
@@ -386,11 +299,6 @@ static size_t dconv_workspace(int N, int B, int E, int H, int W, bool backward, 
     }
     return sizeof(float) * (kt + (backward ? rows * (tiles + 1) : 0));
 }
-static bool dconv_query_ok(int N, int B, int E, int H, int W) {
-    return N >= 1 && B >= 1 && B <= BXI_MAX_IMAGES && E >= 1 && E <= BXI_DCONV_MAX_E && H >= 1 && W >= 1 && fits_i32((int64_t)H * W) &&
-           fits_i32((int64_t)N * H * W);
-}
-
 static int dconv_gather(const DconvTable& t, const int64_t* cells, const DconvSpace& sp, int32_t* status, int E, hipStream_t s) {
     BXI_LAUNCH("solo_dconv_gather", s, dconv_gather_kernel, dim3((unsigned)sp.slots, 4), dim3(kDcThreads), 0, s, t, cells, sp.kT, status, E);
     return check_launch();

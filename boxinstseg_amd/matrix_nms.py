@@ -236,21 +236,24 @@ def discobox_get_seg_single(cate_preds, seg_preds, kernel_preds, featmap_size, i
     """``DiscoBoxSOLOv2Head.get_seg_single`` (discobox_head.py:1560-1660).  ``seg_preds`` [1, C, h, w] is the mask feature and
     ``kernel_preds`` [sum(grid^2), C] the dynamic 1x1 kernels; with ``conv='torch'`` the convolution and the sigmoid run in torch in the
     tensors' own precision (the reference runs this method under autocast), with ``conv='hip'`` in ``solo_candidate_masks`` (fp32, the
-    candidates' kernel rows read in place); the block after them through ``seg_nms`` in fp32."""
+    candidates' kernel rows read in place), with ``conv='hip_half'`` in ``solo_candidate_masks(compute='half', out_dtype=torch.float32)``
+    on fp16 or bf16 ``seg_preds`` / ``kernel_preds`` (read in place, fp32 accumulation, fp32 probabilities); the block after them through
+    ``seg_nms`` in fp32."""
     need_cuda(cate_preds=cate_preds, seg_preds=seg_preds, kernel_preds=kernel_preds)
     assert len(cate_preds) == len(kernel_preds)
-    if conv not in ('torch', 'hip'):
-        raise ValueError(f"conv must be 'torch' or 'hip', got {conv!r}")
+    if conv not in ('torch', 'hip', 'hip_half'):
+        raise ValueError(f"conv must be 'torch', 'hip' or 'hip_half', got {conv!r}")
     inds = cate_preds > cfg_require(cfg, 'score_thr')
     cate_scores = cate_preds[inds]
     if len(cate_scores) == 0:
         return _empty_results(img_meta, cate_scores)
     inds = inds.nonzero()
     cate_labels = inds[:, 1]
-    if conv == 'hip':
+    if conv != 'torch':
         from .solo_conv import solo_candidate_masks
         level = _level_strides(kernel_preds, cate_labels, seg_num_grids, strides)[inds[:, 0]]
-        probs = solo_candidate_masks(seg_preds, kernel_preds, inds[:, 0])
+        half = dict(compute='half', out_dtype=torch.float32) if conv == 'hip_half' else {}
+        probs = solo_candidate_masks(seg_preds, kernel_preds, inds[:, 0], **half)
         return _seg_tail(probs, cate_labels, cate_scores, level.float(), featmap_size, img_meta, cfg)
     kernel_preds = kernel_preds[inds[:, 0]]
     level = _level_strides(kernel_preds, cate_labels, seg_num_grids, strides)[inds[:, 0]]

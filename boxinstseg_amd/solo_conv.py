@@ -10,8 +10,15 @@ There is no CPU or PyTorch fallback: CPU tensors raise.  The kernel values are g
 an image is read once per call, and all levels and images are one call forward (a small gather of the kernel values into scratch and ONE
 launch for the product) and one call backward (the gather, the main kernel, the reduction of grad_kernel's per-tile sums and the pass that
 writes every element of every gradient map).  Around the call torch concatenates the grid_order entries into one int64 vector and zeroes
-the status word.  DEVIATION: fp32 only -- half-precision tensors are upcast here and the
-masks are fp32 (the reference runs these statements under fp16 autocast); every logit is one fp32 fmaf chain over e ascending.
+the status word.  Two precisions, chosen with ``compute``:
+
+    compute='fp32' (default)  every operand fp32 -- half-precision tensors are upcast here and the masks are fp32; every logit is one
+                              fp32 fmaf chain over e ascending.  DEVIATION from the reference, which runs these statements under fp16
+                              autocast: its own precision is ``compute='half'``.
+    compute='half'            csrc/solo_dconv16.hip, include/boxinst/boxinst_hip_dconv16.h: fp16 or bf16 tensors read in place (no upcast
+                              copy, no cast of the gradients), fp32 accumulation on v_mfma_f32_32x32x16_{f16,bf16}, masks in the inputs'
+                              dtype as autocast gives them (or fp32 with ``out_dtype=torch.float32``), gradients in the inputs' dtype.
+                              fp32 or mixed input raises: there is no silent cast.
 """
 from __future__ import annotations
 
@@ -118,12 +125,94 @@ def _lists(plan, out, img):
     return masks, inds
 
 
-def _run(plan, kernel_preds_raw, ins_pred):
-    out, img = _DynamicMasks.apply(plan, _fp32(ins_pred), *[_fp32(m) for m in kernel_preds_raw])
+def _run(plan, kernel_preds_raw, ins_pred, compute='fp32', out_dtype=None):
+    if compute == 'half':
+        plan.out_dtype = out_dtype or ins_pred.dtype
+        out, img = _DynamicMasks16.apply(plan, ins_pred.contiguous(), *[m.contiguous() for m in kernel_preds_raw])
+    else:
+        out, img = _DynamicMasks.apply(plan, _fp32(ins_pred), *[_fp32(m) for m in kernel_preds_raw])
     return _lists(plan, out, img)
 
 
-def solo_dynamic_masks(kernel_preds_raw, grid_order, ins_pred, sigmoid=True, status=None):
+_HALF = {torch.float16: _lib.DCONV16_F16, torch.bfloat16: _lib.DCONV16_BF16}
+
+
+def _check_compute(compute, out_dtype, **tensors):
+    """``compute`` is 'fp32' or 'half'; with 'half' every tensor is of ONE half dtype (checked before anything else, so that it is said
+    without a device) and ``out_dtype`` is None, that dtype or torch.float32; with 'fp32' the masks are fp32."""
+    if compute not in ('fp32', 'half'):
+        raise ValueError(f"compute must be 'fp32' or 'half', got {compute!r}")
+    if compute == 'fp32':
+        if out_dtype not in (None, torch.float32):
+            raise RuntimeError(f"compute='fp32' returns fp32 masks, got out_dtype={out_dtype}")
+        return
+    dtypes = {name: t.dtype for name, t in tensors.items() if t is not None}
+    first = next(iter(dtypes.values()))
+    if first not in _HALF or any(d != first for d in dtypes.values()):
+        raise RuntimeError("compute='half' takes tensors of one half dtype, torch.float16 or torch.bfloat16, and casts nothing: got "
+                           + ', '.join(f'{n} {d}' for n, d in dtypes.items()))
+    if out_dtype not in (None, first, torch.float32):
+        raise RuntimeError(f"compute='half' returns masks in the inputs' dtype {first} or in torch.float32, got out_dtype={out_dtype}")
+
+
+def _out_code(plan, dtype):
+    return _lib.DCONV16_OUT_F32 if plan.out_dtype == torch.float32 else _HALF[dtype]
+
+
+def _call_forward16(plan, feat, maps):
+    lib = _lib.load()
+    dev = feat.device
+    B, E, H, W = feat.shape
+    out = torch.empty((plan.N, H, W), dtype=plan.out_dtype, device=dev)
+    img = torch.empty((plan.N,), dtype=torch.int64, device=dev)
+    ws_bytes = lib.bxi_solo_dconv16_forward_workspace_bytes(plan.N, B, E)
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check('bxi_solo_dconv16_forward', lib.bxi_solo_dconv16_forward(
+            feat.data_ptr(), _HALF[feat.dtype], B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps),
+            plan.layout, None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(),
+            _out_code(plan, feat.dtype), img.data_ptr(), plan.status.data_ptr(), ws.data_ptr(), ws_bytes, current_stream(dev)))
+    return out, img
+
+
+class _DynamicMasks16(torch.autograd.Function):
+    """``compute='half'``: the tensors as they are, the masks in ``plan.out_dtype``, the gradients in the inputs' dtype."""
+
+    @staticmethod
+    def forward(ctx, plan, feat, *maps):
+        out, img = _call_forward16(plan, feat, maps)
+        ctx.plan = plan
+        ctx.save_for_backward(feat, out, *maps)
+        ctx.mark_non_differentiable(img)
+        return out, img
+
+    @staticmethod
+    def backward(ctx, g_out, _g_img):
+        plan = ctx.plan
+        feat, out, *maps = ctx.saved_tensors
+        need_feat, need_maps = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        if not (need_feat or need_maps):
+            return (None, None) + (None,) * len(maps)
+        lib = _lib.load()
+        dev = feat.device
+        B, E, H, W = feat.shape
+        g = g_out.detach().to(out.dtype).contiguous()                      # autograd hands it over in the masks' dtype: no copy
+        g_feat = torch.empty_like(feat) if need_feat else None
+        g_maps = [torch.empty_like(m) for m in maps] if need_maps else None
+        ws_bytes = lib.bxi_solo_dconv16_backward_workspace_bytes(plan.N, B, E, H, W)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check('bxi_solo_dconv16_backward', lib.bxi_solo_dconv16_backward(
+                feat.data_ptr(), _HALF[feat.dtype], B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids),
+                len(maps), plan.layout, None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act,
+                out.data_ptr(), g.data_ptr(), _out_code(plan, feat.dtype), None if g_feat is None else g_feat.data_ptr(),
+                None if g_maps is None else _lib.ptr_array([m.data_ptr() for m in g_maps]), plan.status.data_ptr(), ws.data_ptr(), ws_bytes,
+                current_stream(dev)))
+        grads = [gm if need else None for gm, need in zip(g_maps, ctx.needs_input_grad[2:])] if need_maps else [None] * len(maps)
+        return (None, g_feat, *grads)
+
+
+def solo_dynamic_masks(kernel_preds_raw, grid_order, ins_pred, sigmoid=True, status=None, compute='fp32', out_dtype=None):
     """The masks of the assigned grid cells.  ``kernel_preds_raw``: a list over levels of [B,E,S,S]; ``grid_order``: ``SoloTargets.grid_order``
     ([level][image] int64 on the device, sizes known on the host) or the ``SoloTargets`` object; ``ins_pred`` [B,E,H,W].  Returns
     ``(masks, img_inds)``: per level the fp32 masks [N_l,H,W] of its images concatenated in order (``sigmoid`` of the logits, or the logits) and
@@ -131,28 +220,39 @@ def solo_dynamic_masks(kernel_preds_raw, grid_order, ins_pred, sigmoid=True, sta
     views of one [N,H,W] buffer.  Gradients reach the kernel maps and ``ins_pred`` where they require them: every element of a map gets one,
     zero for a cell nobody selected and the sum of its rows' for a cell ``grid_order`` names more than once.  A cell outside its map gives the
     masks of an all-zero kernel and sets ``status[0]`` (int32 [1] on the device, a fresh zero when not given) to 1; nothing reads it back
-    here."""
+    here.  ``compute='half'``: fp16 or bf16 tensors read in place (the module's docstring); the masks are then of the inputs' dtype, or fp32
+    with ``out_dtype=torch.float32``."""
+    kernel_preds_raw = list(kernel_preds_raw)
+    _check_compute(compute, out_dtype, ins_pred=ins_pred, **{f'kernel_preds_raw[{l}]': m for l, m in enumerate(kernel_preds_raw)})
     plan = _plan(kernel_preds_raw, grid_order, ins_pred, sigmoid, status)
-    return _run(plan, kernel_preds_raw, ins_pred)
+    return _run(plan, kernel_preds_raw, ins_pred, compute, out_dtype)
 
 
-def solo_dynamic_masks_pair(s_kernel_preds_raw, t_kernel_preds_raw, grid_order, s_ins_pred, t_ins_pred, sigmoid=True, status=None):
+def solo_dynamic_masks_pair(s_kernel_preds_raw, t_kernel_preds_raw, grid_order, s_ins_pred, t_ins_pred, sigmoid=True, status=None,
+                            compute='fp32', out_dtype=None):
     """``solo_dynamic_masks`` for the student and for the independent teacher with one ``grid_order``: the call ``loss`` and ``corr_loss``
     make.  The teacher runs without a backward (its tensors are detached).  Returns ``(s_masks, t_masks, img_inds)``.  Nothing is kept from
-    one call to the next."""
+    one call to the next.  ``compute`` and ``out_dtype`` as in ``solo_dynamic_masks``, for both legs: all tensors of one half dtype."""
+    s_kernel_preds_raw, t_kernel_preds_raw = list(s_kernel_preds_raw), list(t_kernel_preds_raw)
+    _check_compute(compute, out_dtype, s_ins_pred=s_ins_pred, t_ins_pred=t_ins_pred,
+                   **{f's_kernel_preds_raw[{l}]': m for l, m in enumerate(s_kernel_preds_raw)},
+                   **{f't_kernel_preds_raw[{l}]': m for l, m in enumerate(t_kernel_preds_raw)})
     plan = _plan(s_kernel_preds_raw, grid_order, s_ins_pred, sigmoid, status)
     t_plan = _plan(t_kernel_preds_raw, grid_order, t_ins_pred, sigmoid, plan.status)
     t_plan.cells = plan.cells
-    s_masks, inds = _run(plan, s_kernel_preds_raw, s_ins_pred)
+    s_masks, inds = _run(plan, s_kernel_preds_raw, s_ins_pred, compute, out_dtype)
     with torch.no_grad():
-        t_masks, _ = _run(t_plan, [m.detach() for m in t_kernel_preds_raw], t_ins_pred.detach())
+        t_masks, _ = _run(t_plan, [m.detach() for m in t_kernel_preds_raw], t_ins_pred.detach(), compute, out_dtype)
     return s_masks, t_masks, inds
 
 
-def solo_candidate_masks(seg_pred, kernel_preds, rows=None, sigmoid=True, status=None):
+def solo_candidate_masks(seg_pred, kernel_preds, rows=None, sigmoid=True, status=None, compute='fp32', out_dtype=None):
     """``F.conv2d(seg_pred, kernel_preds[rows].view(I, E, 1, 1)).squeeze(0).sigmoid()`` of get_seg_single: ``seg_pred`` [1,E,h,w] the mask
     feature, ``kernel_preds`` [sum(grid^2),E] read in place through ``rows`` (int64 [I] on the device, any order, repeats allowed; every row
-    when None).  Returns [I,h,w] fp32 probabilities (logits with ``sigmoid=False``), ready for ``seg_nms``.  No gradient."""
+    when None).  Returns [I,h,w] fp32 probabilities (logits with ``sigmoid=False``), ready for ``seg_nms``.  No gradient.
+    ``compute='half'``: fp16 or bf16 ``seg_pred`` and ``kernel_preds`` read in place, fp32 accumulation, the result in their dtype or, with
+    ``out_dtype=torch.float32``, in fp32."""
+    _check_compute(compute, out_dtype, seg_pred=seg_pred, kernel_preds=kernel_preds)
     need_cuda(seg_pred=seg_pred, kernel_preds=kernel_preds, rows=rows)
     if seg_pred.dim() != 4 or seg_pred.shape[0] != 1 or kernel_preds.dim() != 2 or kernel_preds.shape[1] != seg_pred.shape[1]:
         raise RuntimeError(f'seg_pred must be [1,E,h,w] and kernel_preds [rows,E], got {tuple(seg_pred.shape)} and {tuple(kernel_preds.shape)}')
@@ -164,5 +264,8 @@ def solo_candidate_masks(seg_pred, kernel_preds, rows=None, sigmoid=True, status
     plan = types.SimpleNamespace(layout=_lib.DCONV_ROWS, grids=[max(int(kernel_preds.shape[0]), 1)], counts=[n], N=n,
                                  cells=None if rows is None else rows.contiguous(), act=_lib.DCONV_SIGMOID if sigmoid else _lib.DCONV_NONE,
                                  status=status, L=1, B=1)
+    if compute == 'half':
+        plan.out_dtype = out_dtype or seg_pred.dtype
+        return _call_forward16(plan, seg_pred.detach().contiguous(), [kernel_preds.detach().contiguous()])[0]
     out, _ = _call_forward(plan, _fp32(seg_pred.detach()), [_fp32(kernel_preds.detach())])
     return out

@@ -12,9 +12,10 @@
  *     :1275-1279  the sigmoid of a level's masks           :936-1000, :1018-1022  the same block in corr_loss
  *     :1607-1608  get_seg_single: F.conv2d(seg_preds, kernel_preds.view(I, N, 1, 1)).squeeze(0).sigmoid()
  *
- * DEVIATION: fp32 only.  The reference runs these statements under fp16 autocast; here every operand is fp32, every logit is ONE fp32
- * chain fma(k(i,E-1), f(E-1,p), ... fma(k(i,0), f(0,p), 0)) over e = 0 .. E-1 in ascending order (v_mfma_f32_32x32x2_f32, bit for bit a
- * k-ordered fmaf chain), and the result is fp32.
+ * DEVIATION: this family is fp32.  The reference runs these statements under fp16 autocast; here every operand is fp32, every logit is
+ * ONE fp32 chain fma(k(i,E-1), f(E-1,p), ... fma(k(i,0), f(0,p), 0)) over e = 0 .. E-1 in ascending order (v_mfma_f32_32x32x2_f32, bit
+ * for bit a k-ordered fmaf chain), and the result is fp32.  The reference's own precision -- fp16 or bf16 tensors read in place, fp32
+ * accumulation -- is the sibling family of boxinst_hip_dconv16.h.
  *
  * Rows and segments.  The N output rows are ordered as the reference concatenates them: level-major, inside a level image by image,
  * inside an image in grid_order's order.  `seg_counts` (HOST, [L*B], index l*B + b) holds the number of rows of every (level, image)
