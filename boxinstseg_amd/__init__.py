@@ -40,6 +40,10 @@ Public surface (mirrors the reference's for this path):
     solo_candidate_masks               <-> F.conv2d(seg_preds, kernel_preds[rows]).sigmoid() of get_seg_single, the kernel rows read in place
       (all three) compute='half'       : the same statements as the reference's autocast runs them -- fp16 / bf16 tensors read in place,
                                          fp32 accumulation, half masks and gradients (csrc/solo_dconv16.hip); discobox_get_seg_single(conv='hip_half')
+    box_solov2_ins_preds               <-> BoxSOLOv2Head.forward :205-216 + loss :317-320: the set cells' dynamic convolution and the per-level bilinear
+                                         resize, nothing of all cells' size (csrc/solo_dconv_level.hip; autograd, fp32)
+    box_solov2_set_cells               : the set cells of every (level, image) of a SoloTargets, ascending, without a host synchronisation
+    box_solov2_get_seg_single_kernels  <-> BoxSOLOv2Head.get_seg_single from the mask feature and the kernels: only the candidates' masks exist
     box2mask_attn_mask, attn_mask_bits <-> the attention mask of Box2MaskHead.forward_head and its repair in forward, as bits (PackedAttnMask), one launch
     pack_attn_mask                     : an existing bool attention mask [B*M,Q,S] or [Q,S] packed to a PackedAttnMask on the device
     masked_attention                   : the attention core of torch.nn.MultiheadAttention with that mask, forward and backward, no [Q,S] tensor
@@ -67,6 +71,7 @@ from .corr import ObjectBank, SemanticCorrSolver, corr_objects, parse_corr_cfg, 
 from .roi_align import RoIAlign, corr_level, relu_and_l2_norm_feat, roi_align, roi_feat_norm, sigmoid_roi_masks, target_boxes
 from .msda import MultiScaleDeformableAttention, multi_scale_deformable_attn, multi_scale_deformable_attn_fused
 from .solo_conv import solo_candidate_masks, solo_dynamic_masks, solo_dynamic_masks_pair
+from .box_solo_masks import box_solov2_get_seg_single_kernels, box_solov2_ins_preds, box_solov2_set_cells
 from .masked_attn import MultiheadAttention, PackedAttnMask, attn_mask_bits, box2mask_attn_mask, masked_attention, pack_attn_mask
 from .inst_post import MaskFormerFusionHead, box2mask_format_results, box2mask_instances, instance_topk
 from .config import load_config
@@ -87,6 +92,7 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'roi_align', 'RoIAlign', 'relu_and_l2_norm_feat', 'roi_feat_norm', 'sigmoid_roi_masks', 'target_boxes', 'corr_level',
            'multi_scale_deformable_attn', 'multi_scale_deformable_attn_fused', 'MultiScaleDeformableAttention', 'ATTENTION', 'build_attention',
            'solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks',
+           'box_solov2_ins_preds', 'box_solov2_set_cells', 'box_solov2_get_seg_single_kernels',
            'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention',
            'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results']
 __version__ = '0.1.0'

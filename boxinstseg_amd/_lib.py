@@ -354,6 +354,25 @@ HALF_FAMILIES = [
     ('dconv16', ('include/boxinst/boxinst_hip_dconv16.h',), DCONV16_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_dconvl.h (BoxLevelSet's training masks: the assigned cells' dynamic convolution and the per-level bilinear resize)
+DCONVL_MAX_DOWN, DCONVL_MAX_UP = 8, 2
+DCONVL_SIGNATURES = {
+    'bxi_solo_dconvl_forward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), c_int]),
+    'bxi_solo_dconvl_forward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), c_int,
+                                            c_void_p, C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_solo_dconvl_backward_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), c_int]),
+    'bxi_solo_dconvl_backward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), c_int,
+                                             c_void_p, C.POINTER(c_int), c_int, c_void_p, c_void_p, C.POINTER(c_void_p), c_void_p, c_void_p,
+                                             c_size_t, c_void_p]),
+}
+
+# the families on top of the dynamic convolution: a fourth list, because tests/test_abi_family_dconv16.py pins HALF_FAMILIES to
+# ['dconv16']; the same triples, applied by load() behind the other three with the same check across all lists
+# (tests/test_abi_family_dconvl.py)
+LEVEL_FAMILIES = [
+    ('dconvl', ('include/boxinst/boxinst_hip_dconvl.h',), DCONVL_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -375,7 +394,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')
