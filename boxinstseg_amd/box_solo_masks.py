@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._common import cfg_require, current_stream, need_cuda
+from .solo_conv import _backward
 
 __all__ = ['box_solov2_ins_preds', 'box_solov2_set_cells', 'box_solov2_get_seg_single_kernels']
 
@@ -58,26 +59,17 @@ class _InsPreds(torch.autograd.Function):
     def backward(ctx, g_out):
         plan = ctx.plan
         feat, *maps = ctx.saved_tensors
-        need_feat, need_maps = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        if not (need_feat or need_maps):
-            return (None, None) + (None,) * len(maps)
-        lib = _lib.load()
-        dev = feat.device
         B, E, H, W = feat.shape
-        g = g_out.detach().to(torch.float32).contiguous()
-        g_feat = torch.empty_like(feat) if need_feat else None
-        g_maps = [torch.empty_like(m) for m in maps] if need_maps else None
         sizes, counts = _sizes_flat(plan), _lib.int_array(plan.counts)
-        ws_bytes = lib.bxi_solo_dconvl_backward_workspace_bytes(B, E, H, W, sizes, counts, plan.L)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
+
+        def call(lib, g, g_feat, g_maps, ws, ws_bytes, stream):
             _lib.check_supported('bxi_solo_dconvl_backward_f32', lib.bxi_solo_dconvl_backward_f32(
                 feat.data_ptr(), B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), sizes, plan.L,
-                None if plan.cells is None else plan.cells.data_ptr(), counts, plan.N, g.data_ptr(),
-                None if g_feat is None else g_feat.data_ptr(), None if g_maps is None else _lib.ptr_array([m.data_ptr() for m in g_maps]),
-                plan.status.data_ptr(), ws.data_ptr(), ws_bytes, current_stream(dev)), HEADER)
-        grads = [gm if need else None for gm, need in zip(g_maps, ctx.needs_input_grad[2:])] if need_maps else [None] * len(maps)
-        return (None, g_feat, *grads)
+                None if plan.cells is None else plan.cells.data_ptr(), counts, plan.N, g, g_feat, g_maps, plan.status.data_ptr(), ws,
+                ws_bytes, stream), HEADER)
+
+        return _backward(ctx, g_out, torch.float32, feat, maps,
+                         lambda lib: lib.bxi_solo_dconvl_backward_workspace_bytes(B, E, H, W, sizes, counts, plan.L), call)
 
 
 def _supported(H, W, sizes):

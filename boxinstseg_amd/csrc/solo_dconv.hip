@@ -9,7 +9,12 @@
 // v_mfma_f32_32x32x2_f32: lane l holds A[row l&31][k l>>5] and B[k l>>5][column l&31], the result has its column on the lane and rows
 // (reg&3) + 8 (reg>>2) + 4 (l>>5) in its 16 registers, and every element is one fmaf chain in ascending k.
 //
-// dconv_gather_kernel   one workgroup per (chunk, quarter of E): kT from the maps (or from the test-time matrix) through the cells.
+// Here: the two product kernels, their kT layout (kt_at, the tag Kt) and the two entry points.  The gather, the reduction, the pass over
+// the gradient maps, the pointer checks, the workspace carve and the launches of the three small kernels are solo_dconv_device.hpp's,
+// shared with solo_dconv16.hip.
+//
+// dconv_gather_kernel<float, Kt>  (solo_dconv_device.hpp) one workgroup per (chunk, quarter of E): kT from the maps (or from the test-time
+//   matrix) through the cells.
 // dconv_fwd_kernel<P>   one workgroup = one tile of P pixels of one image.  The tile's E x P feature values go to LDS once; then every
 //   wave takes chunks of 32 of the image's rows (A rows = instances, B / C columns = pixels: a pixel stays on its lane, the stores are
 //   coalesced), k = e ascending.  An image without rows returns before it reads anything.
@@ -18,8 +23,9 @@
 //   ascending; grad_kernel's per-tile partial is A = g [i][pixel], B = the feature block [pixel][e] (staged through LDS, read coalesced),
 //   k = the tile's pixels ascending, stored to part[tile][row][e].
 // dconv_reduce_kernel   (solo_dconv_device.hpp) gk[row][e] = the partials of the row's image's tiles, 32 interleaved sums added in order.
-// dconv_scatter_kernel  every element of every gradient map: the sum of gk over the rows of its segment that name its cell, in row order.
-#include "solo_dconv_device.hpp"                     // the table, locate(), acc_row() and the argument checks, shared with solo_dconv16.hip
+// dconv_scatter_kernel<float, false>  (solo_dconv_device.hpp) every element of every gradient map: the sum of gk over the rows of its
+//   segment that name its cell, in row order.
+#include "solo_dconv_device.hpp"
 
 namespace bxi {
 
@@ -38,34 +44,10 @@ __host__ __device__ __forceinline__ int e8_of(int E) { return (E + 7) & ~7; }
 __device__ __forceinline__ size_t kt_at(int E8, int chunk, int e, int r) {
     return (size_t)chunk * E8 * 32 + (size_t)((e >> 3) * 2 + (e & 1)) * 128 + r * 4 + ((e >> 1) & 3);
 }
-// where kernel(row, e = 0) lies and the stride between channels; nullptr for no row or a cell outside its map (never read)
-__device__ __forceinline__ const float* kernel_of(const DconvTable& t, const int64_t* cells, int b, int row, int lev, int E, int& estride,
-                                                  int32_t* status) {
-    estride = 0;
-    if (row < 0) return nullptr;
-    const int64_t cell = cells ? cells[row] : (int64_t)row;
-    const int ncell = t.cells[lev];
-    if (cell < 0 || cell >= ncell) {
-        *status = BXI_DCONV_STATUS_BAD_CELL;
-        return nullptr;
-    }
-    if (t.layout == BXI_DCONV_ROWS) { estride = 1; return t.maps[0] + (size_t)cell * E; }
-    estride = ncell;
-    return t.maps[lev] + (size_t)b * E * ncell + cell;
-}
-
-__global__ void __launch_bounds__(kDcThreads) dconv_gather_kernel(const DconvTable t, const int64_t* __restrict__ cells, float* __restrict__ kT,
-                                                                  int32_t* status, int E) {
-    const int chunk = blockIdx.x, E8 = e8_of(E), r = threadIdx.x & 31;
-    int b = 0;
-    while (b + 1 < t.B && chunk >= t.chunk0[b + 1]) ++b;
-    int lev = 0, estride;
-    const int row = chunk < t.chunk0[t.B] ? locate(t, b, (chunk - t.chunk0[b]) * 32 + r, lev) : -1;      // a slot past the last chunk: zeros
-    const float* kp = kernel_of(t, cells, b, row, lev, E, estride, status);
-    const int per = (E8 + (int)gridDim.y - 1) / (int)gridDim.y, e_end = min(E8, ((int)blockIdx.y + 1) * per);
-    for (int e = blockIdx.y * per + (threadIdx.x >> 5); e < e_end; e += kDcThreads / 32)
-        kT[kt_at(E8, chunk, e, r)] = (kp && e < E) ? kp[(size_t)e * estride] : 0.f;
-}
+struct Kt {                                                          // the layout tag of dconv_gather_kernel
+    static __host__ __device__ __forceinline__ int round(int E) { return e8_of(E); }
+    static __device__ __forceinline__ size_t at(int E8, int chunk, int e, int r) { return kt_at(E8, chunk, e, r); }
+};
 
 template <int P>
 __global__ void __launch_bounds__(kDcThreads) dconv_fwd_kernel(const DconvTable t, const float* __restrict__ feat, const float* __restrict__ kT,
@@ -269,46 +251,16 @@ __global__ void __launch_bounds__(kDcThreads) dconv_bwd_kernel(const DconvTable 
     }
 }
 
-__global__ void __launch_bounds__(kDcThreads) dconv_scatter_kernel(const DconvTable t, const int64_t* __restrict__ cells,
-                                                                   const float* __restrict__ gk, int E) {
-    const int l = blockIdx.y, ncell = t.cells[l];
-    const int64_t total = (int64_t)(t.layout == BXI_DCONV_ROWS ? 1 : t.B) * E * ncell;
-    const int64_t idx = (int64_t)blockIdx.x * kDcThreads + threadIdx.x;
-    if (idx >= total) return;
-    int b, e, cell;
-    if (t.layout == BXI_DCONV_ROWS) { b = 0; cell = (int)(idx / E); e = (int)(idx % E); }
-    else { cell = (int)(idx % ncell); e = (int)((idx / ncell) % E); b = (int)(idx / ncell / E); }
-    const int i0 = t.start[l * t.B + b], i1 = t.start[l * t.B + b + 1];
-    float s = 0.f;
-    for (int i = i0; i < i1; ++i)
-        if ((cells ? cells[i] : (int64_t)i) == cell) s += gk[(size_t)i * E + e];
-    t.gmaps[l][idx] = s;
-}
-
-// kT [slots][E8][32] with slots = N / 32 + B (never fewer than the chunks: sum_b ceil(n_b / 32)), then for the backward part [tiles][N][E]
-// and gk [N][E], back to back: floats only, kT a multiple of 128 bytes, no padding, so every byte of the workspace is written
-struct DconvSpace { float *kT, *part, *gk; int slots; };
-static size_t dconv_workspace(int N, int B, int E, int H, int W, bool backward, void* base, DconvSpace* sp) {
-    const size_t slots = (size_t)N / 32 + B, kt = slots * e8_of(E) * 32, rows = (size_t)N * E;
-    const size_t tiles = backward ? ((size_t)H * W + BXI_DCONV_TILE - 1) / BXI_DCONV_TILE : 0;
-    if (sp) {
-        sp->kT = static_cast<float*>(base);
-        sp->part = sp->kT + kt;
-        sp->gk = sp->part + tiles * rows;
-        sp->slots = (int)slots;
-    }
-    return sizeof(float) * (kt + (backward ? rows * (tiles + 1) : 0));
-}
-static int dconv_gather(const DconvTable& t, const int64_t* cells, const DconvSpace& sp, int32_t* status, int E, hipStream_t s) {
-    BXI_LAUNCH("solo_dconv_gather", s, dconv_gather_kernel, dim3((unsigned)sp.slots, 4), dim3(kDcThreads), 0, s, t, cells, sp.kT, status, E);
-    return check_launch();
+// the workspace: kT as floats in the layout of kt_at, the backward's tiles of BXI_DCONV_TILE pixels
+static size_t dconv32_workspace(int N, int B, int E, int H, int W, bool backward, void* base, DconvSpace<float>* sp) {
+    return dconv_workspace<float>(e8_of(E), BXI_DCONV_TILE, N, B, E, H, W, backward, base, sp);
 }
 
 }  // namespace bxi
 
 extern "C" size_t bxi_solo_dconv_forward_workspace_bytes(int N, int B, int E) {
     using namespace bxi;
-    return dconv_query_ok(N, B, E, 1, 1) ? dconv_workspace(N, B, E, 1, 1, false, nullptr, nullptr) : 0;
+    return dconv_query_ok(N, B, E, 1, 1) ? dconv32_workspace(N, B, E, 1, 1, false, nullptr, nullptr) : 0;
 }
 
 extern "C" int bxi_solo_dconv_forward_f32(const float* feat, int B, int E, int H, int W, const void* const* kernel_maps, const int* grids, int L,
@@ -319,12 +271,11 @@ extern "C" int bxi_solo_dconv_forward_f32(const float* feat, int B, int E, int H
     int rc = dconv_table(B, E, H, W, kernel_maps, grids, L, layout, seg_counts, N, activation, t);
     if (rc != BXI_OK) return rc;
     if (N == 0) return BXI_OK;
-    if (!feat || !out || !status || (!cells && layout == BXI_DCONV_MAPS)) return BXI_ERR_NULL_POINTER;
-    for (int l = 0; l < L; ++l)
-        if (!t.maps[l]) return BXI_ERR_NULL_POINTER;
+    rc = dconv_forward_args(t, feat, out, status, cells);
+    if (rc != BXI_OK) return rc;
     if (!workspace_ok(workspace, workspace_bytes, bxi_solo_dconv_forward_workspace_bytes(N, B, E), 16)) return BXI_ERR_WORKSPACE;
-    DconvSpace sp;
-    dconv_workspace(N, B, E, H, W, false, workspace, &sp);
+    DconvSpace<float> sp;
+    dconv32_workspace(N, B, E, H, W, false, workspace, &sp);
     const int HW = H * W, E8 = e8_of(E);
     const bool wide = E <= 512;                                      // 64 pixels while the tile fits 128 KB of LDS
     const int P = wide ? 64 : 32, tiles = (HW + P - 1) / P;
@@ -335,7 +286,7 @@ extern "C" int bxi_solo_dconv_forward_f32(const float* feat, int B, int E, int H
         if (e != hipSuccess) { set_last_hip_error((int)e); return BXI_ERR_LAUNCH; }
     }
     hipStream_t s = as_stream(stream);
-    rc = dconv_gather(t, cells, sp, status, E, s);
+    rc = dconv_gather<float, Kt>("solo_dconv_gather", t, cells, sp, status, E, s);
     if (rc != BXI_OK) return rc;
     const dim3 grid((unsigned)((int64_t)B * tiles));
     const int vec = !(HW & 3) && aligned(feat, 16);
@@ -346,7 +297,7 @@ extern "C" int bxi_solo_dconv_forward_f32(const float* feat, int B, int E, int H
 
 extern "C" size_t bxi_solo_dconv_backward_workspace_bytes(int N, int B, int E, int H, int W) {
     using namespace bxi;
-    return dconv_query_ok(N, B, E, H, W) ? dconv_workspace(N, B, E, H, W, true, nullptr, nullptr) : 0;
+    return dconv_query_ok(N, B, E, H, W) ? dconv32_workspace(N, B, E, H, W, true, nullptr, nullptr) : 0;
 }
 
 extern "C" int bxi_solo_dconv_backward_f32(const float* feat, int B, int E, int H, int W, const void* const* kernel_maps, const int* grids, int L,
@@ -358,23 +309,14 @@ extern "C" int bxi_solo_dconv_backward_f32(const float* feat, int B, int E, int 
     int rc = dconv_table(B, E, H, W, kernel_maps, grids, L, layout, seg_counts, N, activation, t);
     if (rc != BXI_OK) return rc;
     if (!grad_feat && !grad_kernel_maps) return BXI_OK;
-    if (N > 0) {
-        if (!out || !grad_out || !status || (!cells && layout == BXI_DCONV_MAPS)) return BXI_ERR_NULL_POINTER;
-        if (grad_kernel_maps && !feat) return BXI_ERR_NULL_POINTER;
-        for (int l = 0; l < L; ++l)
-            if (!t.maps[l]) return BXI_ERR_NULL_POINTER;
-    }
-    if (grad_kernel_maps)
-        for (int l = 0; l < L; ++l) {
-            if (!grad_kernel_maps[l]) return BXI_ERR_NULL_POINTER;
-            t.gmaps[l] = static_cast<float*>(grad_kernel_maps[l]);
-        }
-    DconvSpace sp = {nullptr, nullptr, nullptr, 0};
+    rc = dconv_backward_args(t, N, feat, out, grad_out, status, cells, grad_kernel_maps);
+    if (rc != BXI_OK) return rc;
+    DconvSpace<float> sp = {nullptr, nullptr, nullptr, 0};
     hipStream_t s = as_stream(stream);
     if (N > 0) {
         if (!workspace_ok(workspace, workspace_bytes, bxi_solo_dconv_backward_workspace_bytes(N, B, E, H, W), 16)) return BXI_ERR_WORKSPACE;
-        dconv_workspace(N, B, E, H, W, true, workspace, &sp);
-        rc = dconv_gather(t, cells, sp, status, E, s);
+        dconv32_workspace(N, B, E, H, W, true, workspace, &sp);
+        rc = dconv_gather<float, Kt>("solo_dconv_gather", t, cells, sp, status, E, s);
         if (rc != BXI_OK) return rc;
     }
     // without gradient maps the feature is not read and the partial sums are not formed
@@ -385,17 +327,8 @@ extern "C" int bxi_solo_dconv_backward_f32(const float* feat, int B, int E, int 
     rc = check_launch();
     if (rc != BXI_OK || !grad_kernel_maps) return rc;
     if (part) {
-        BXI_LAUNCH("solo_dconv_reduce", s, dconv_reduce_kernel, dim3((unsigned)N, (unsigned)((E + 31) / 32)), dim3(32 * kDcReduceLanes), 0, s, part, sp.gk, E,
-                   tiles, N);
-        rc = check_launch();
+        rc = dconv_reduce("solo_dconv_reduce", part, sp.gk, E, tiles, N, s);
         if (rc != BXI_OK) return rc;
     }
-    int64_t most = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t total = (int64_t)(layout == BXI_DCONV_ROWS ? 1 : B) * E * t.cells[l];
-        most = total > most ? total : most;
-    }
-    BXI_LAUNCH("solo_dconv_scatter", s, dconv_scatter_kernel, dim3((unsigned)((most + kDcThreads - 1) / kDcThreads), (unsigned)L), dim3(kDcThreads), 0, s, t,
-               cells, sp.gk, E);
-    return check_launch();
+    return dconv_scatter<float, false>("solo_dconv_scatter", t, cells, sp.gk, E, s);
 }

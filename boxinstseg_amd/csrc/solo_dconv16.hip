@@ -4,10 +4,14 @@
 // v_mfma_f32_32x32x16_{f16,bf16}: lane l (r = l & 31, h = l >> 5) holds A[row r][k = 8 h + j] and B[k = 8 h + j][column r], j = 0..7, as
 // ONE 16-byte fragment, the fp32 result has its column on the lane and rows acc_row(reg, h) in its 16 registers.
 //
-// dconv16_gather_kernel<BWD>  one workgroup per (chunk of 32 rows, quarter of E): 2-byte copies, the same for both types.  Forward (kT):
-//   per chunk and k step of 16 channels lane l's fragment at [step][l][8]: a wave reads the A operand of a step as one 1 KB piece.
-//   Backward (kR): [chunk][channel][32 rows], the A operand of grad_feat's product (A row = channel, k = rows).  Zeros for a chunk's
-//   missing rows, for the tail of E up to a multiple of 16 and for a cell outside its map.
+// Here: the two product kernels with their four (type, out type) dispatches, their two kT layouts (kt16_at and kr16_at, the tags Kt16 and
+// Kr16) and the two entry points.  The gather, the reduction, the pass over the gradient maps, f2h, the pointer checks, the workspace
+// carve and the launches of the three small kernels are solo_dconv_device.hpp's, shared with solo_dconv.hip.
+//
+// dconv_gather_kernel<h16, Kt16 | Kr16>  (solo_dconv_device.hpp) one workgroup per (chunk of 32 rows, quarter of E): 2-byte copies, the
+//   same for both types.  Forward (Kt16): per chunk and k step of 16 channels lane l's fragment at [step][l][8]: a wave reads the A
+//   operand of a step as one 1 KB piece.  Backward (Kr16): [chunk][channel][32 rows], the A operand of grad_feat's product (A row =
+//   channel, k = rows).  Zeros for a chunk's missing rows, for the tail of E up to a multiple of 16 and for a cell outside its map.
 // dconv16_fwd_kernel    one workgroup = one tile of 64 pixels of one image.  The tile's E16 x 64 feature values go to LDS once,
 //   PIXEL-major ([pixel][E16 + 8]): the B fragment of a lane is one 16-byte read, and a row's 8 extra halves keep the 32 lanes of a
 //   16-byte read on different banks.  Then every wave takes chunks of 32 of the image's rows; sigmoid in fp32, one rounding, stores
@@ -16,15 +20,14 @@
 //   major AND pixel-major.  A wave owns blocks of 32 channels: grad_feat's block is A = kR, B = g pixel-major, k = the image's rows;
 //   grad_kernel's per-tile partial is A = g row-major, B = the feature block [channel][pixel] in LDS, k = the tile's pixels, stored as
 //   fp32 to part[tile][row][e].
-// dconv_reduce_kernel   the fp32 family's (solo_dconv_device.hpp).  dconv16_scatter_kernel: every element of every gradient map, the
-//   fp32 sum of gk over the rows of its segment that name its cell, in row order, rounded once.
+// dconv_reduce_kernel, dconv_scatter_kernel<h16, BF>  (solo_dconv_device.hpp) the fp32 family's reduction; every element of every
+//   gradient map, the fp32 sum of gk over the rows of its segment that name its cell, in row order, rounded once.
 #include "solo_dconv_device.hpp"
 
 #include "../../include/boxinst/boxinst_hip_dconv16.h"
 
 namespace bxi {
 
-typedef uint16_t h16;                                                // a half value's bits, fp16 or bf16
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));      // eight of them: one MFMA fragment
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -38,19 +41,17 @@ __device__ __forceinline__ size_t kt16_at(int E16, int chunk, int e, int r) {
     return (size_t)chunk * E16 * 32 + (size_t)(e >> 4) * 512 + (size_t)((((e >> 3) & 1) * 32 + r) * 8 + (e & 7));
 }
 __device__ __forceinline__ size_t kr16_at(int E16, int chunk, int e, int r) { return ((size_t)chunk * E16 + e) * 32 + r; }
+struct Kt16 {                                                        // the layout tags of dconv_gather_kernel: forward, backward
+    static __host__ __device__ __forceinline__ int round(int E) { return e16_of(E); }
+    static __device__ __forceinline__ size_t at(int E16, int chunk, int e, int r) { return kt16_at(E16, chunk, e, r); }
+};
+struct Kr16 : Kt16 {
+    static __device__ __forceinline__ size_t at(int E16, int chunk, int e, int r) { return kr16_at(E16, chunk, e, r); }
+};
 
 template <bool BF> __device__ __forceinline__ float h2f(h16 v) {
     if constexpr (BF) return __uint_as_float((uint32_t)v << 16);
     else return (float)__builtin_bit_cast(_Float16, v);
-}
-// fp32 -> half, to nearest even; fp16 overflows to inf, a bf16 NaN is 0x7FC0 (as torch's casts)
-template <bool BF> __device__ __forceinline__ h16 f2h(float x) {
-    if constexpr (BF) {
-        const uint32_t u = __float_as_uint(x);
-        return x != x ? (h16)0x7FC0 : (h16)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-    } else {
-        return __builtin_bit_cast(h16, (_Float16)x);
-    }
 }
 template <bool BF, bool F32> __device__ __forceinline__ float load_o(const void* p, size_t at) {
     if constexpr (F32) return static_cast<const float*>(p)[at];
@@ -68,36 +69,6 @@ template <bool BF> __device__ __forceinline__ f16v mfma16(u32x4 a, u32x4 b, f16v
 #else
     return c;
 #endif
-}
-
-// where kernel(row, e = 0) lies and the stride between channels; nullptr for no row or a cell outside its map (never read)
-__device__ __forceinline__ const h16* kernel16_of(const DconvTable& t, const int64_t* cells, int b, int row, int lev, int E, int& estride,
-                                                  int32_t* status) {
-    estride = 0;
-    if (row < 0) return nullptr;
-    const int64_t cell = cells ? cells[row] : (int64_t)row;
-    const int ncell = t.cells[lev];
-    if (cell < 0 || cell >= ncell) {
-        *status = BXI_DCONV_STATUS_BAD_CELL;
-        return nullptr;
-    }
-    if (t.layout == BXI_DCONV_ROWS) { estride = 1; return reinterpret_cast<const h16*>(t.maps[0]) + (size_t)cell * E; }
-    estride = ncell;
-    return reinterpret_cast<const h16*>(t.maps[lev]) + (size_t)b * E * ncell + cell;
-}
-
-template <bool BWD>
-__global__ void __launch_bounds__(kDcThreads) dconv16_gather_kernel(const DconvTable t, const int64_t* __restrict__ cells, h16* __restrict__ kT,
-                                                                    int32_t* status, int E) {
-    const int chunk = blockIdx.x, E16 = e16_of(E), r = threadIdx.x & 31;
-    int b = 0;
-    while (b + 1 < t.B && chunk >= t.chunk0[b + 1]) ++b;
-    int lev = 0, estride;
-    const int row = chunk < t.chunk0[t.B] ? locate(t, b, (chunk - t.chunk0[b]) * 32 + r, lev) : -1;      // a slot past the last chunk: zeros
-    const h16* kp = kernel16_of(t, cells, b, row, lev, E, estride, status);
-    const int per = (E16 + (int)gridDim.y - 1) / (int)gridDim.y, e_end = min(E16, ((int)blockIdx.y + 1) * per);
-    for (int e = blockIdx.y * per + (threadIdx.x >> 5); e < e_end; e += kDcThreads / 32)
-        kT[BWD ? kr16_at(E16, chunk, e, r) : kt16_at(E16, chunk, e, r)] = (kp && e < E) ? kp[(size_t)e * estride] : (h16)0;
 }
 
 template <bool BF, bool F32>
@@ -314,36 +285,10 @@ __global__ void __launch_bounds__(kDcThreads) dconv16_bwd_kernel(const DconvTabl
     }
 }
 
-template <bool BF>
-__global__ void __launch_bounds__(kDcThreads) dconv16_scatter_kernel(const DconvTable t, const int64_t* __restrict__ cells,
-                                                                     const float* __restrict__ gk, int E) {
-    const int l = blockIdx.y, ncell = t.cells[l];
-    const int64_t total = (int64_t)(t.layout == BXI_DCONV_ROWS ? 1 : t.B) * E * ncell;
-    const int64_t idx = (int64_t)blockIdx.x * kDcThreads + threadIdx.x;
-    if (idx >= total) return;
-    int b, e, cell;
-    if (t.layout == BXI_DCONV_ROWS) { b = 0; cell = (int)(idx / E); e = (int)(idx % E); }
-    else { cell = (int)(idx % ncell); e = (int)((idx / ncell) % E); b = (int)(idx / ncell / E); }
-    const int i0 = t.start[l * t.B + b], i1 = t.start[l * t.B + b + 1];
-    float s = 0.f;
-    for (int i = i0; i < i1; ++i)
-        if ((cells ? cells[i] : (int64_t)i) == cell) s += gk[(size_t)i * E + e];
-    reinterpret_cast<h16*>(t.gmaps[l])[idx] = f2h<BF>(s);
-}
-
-// kT [slots][E16][32] halves with slots = N / 32 + B (a multiple of 1 KB), then for the backward part [tiles][N][E] and gk [N][E] as
-// fp32, back to back, no padding: every byte of the workspace is written
-struct Dconv16Space { h16* kT; float *part, *gk; int slots; };
+// the workspace: kT (or kR) as halves, a multiple of 1 KB, the backward's tiles of kP16 pixels
+typedef DconvSpace<h16> Dconv16Space;
 static size_t dconv16_workspace(int N, int B, int E, int H, int W, bool backward, void* base, Dconv16Space* sp) {
-    const size_t slots = (size_t)N / 32 + B, kt = slots * e16_of(E) * 32, rows = (size_t)N * E;
-    const size_t tiles = backward ? ((size_t)H * W + kP16 - 1) / kP16 : 0;
-    if (sp) {
-        sp->kT = static_cast<h16*>(base);
-        sp->part = reinterpret_cast<float*>(sp->kT + kt);
-        sp->gk = sp->part + tiles * rows;
-        sp->slots = (int)slots;
-    }
-    return sizeof(h16) * kt + (backward ? sizeof(float) * rows * (tiles + 1) : 0);
+    return dconv_workspace<h16>(e16_of(E), kP16, N, B, E, H, W, backward, base, sp);
 }
 
 static bool dconv16_types_ok(int dtype, int out_dtype) {
@@ -392,15 +337,13 @@ extern "C" int bxi_solo_dconv16_forward(const void* feat, int dtype, int B, int 
     if (rc != BXI_OK) return rc;
     if (!dconv16_types_ok(dtype, out_dtype)) return BXI_ERR_BAD_ARGUMENT;
     if (N == 0) return BXI_OK;
-    if (!feat || !out || !status || (!cells && layout == BXI_DCONV_MAPS)) return BXI_ERR_NULL_POINTER;
-    for (int l = 0; l < L; ++l)
-        if (!t.maps[l]) return BXI_ERR_NULL_POINTER;
+    rc = dconv_forward_args(t, feat, out, status, cells);
+    if (rc != BXI_OK) return rc;
     if (!workspace_ok(workspace, workspace_bytes, bxi_solo_dconv16_forward_workspace_bytes(N, B, E), 16)) return BXI_ERR_WORKSPACE;
     Dconv16Space sp;
     dconv16_workspace(N, B, E, H, W, false, workspace, &sp);
     hipStream_t s = as_stream(stream);
-    BXI_LAUNCH("solo_dconv16_gather", s, dconv16_gather_kernel<false>, dim3((unsigned)sp.slots, 4), dim3(kDcThreads), 0, s, t, cells, sp.kT, status, E);
-    rc = check_launch();
+    rc = dconv_gather<h16, Kt16>("solo_dconv16_gather", t, cells, sp, status, E, s);
     if (rc != BXI_OK) return rc;
     const h16* f = static_cast<const h16*>(feat);
     const bool f32 = out_dtype == BXI_DCONV16_OUT_F32;
@@ -426,24 +369,14 @@ extern "C" int bxi_solo_dconv16_backward(const void* feat, int dtype, int B, int
     if (rc != BXI_OK) return rc;
     if (!dconv16_types_ok(dtype, out_dtype)) return BXI_ERR_BAD_ARGUMENT;
     if (!grad_feat && !grad_kernel_maps) return BXI_OK;
-    if (N > 0) {
-        if (!out || !grad_out || !status || (!cells && layout == BXI_DCONV_MAPS)) return BXI_ERR_NULL_POINTER;
-        if (grad_kernel_maps && !feat) return BXI_ERR_NULL_POINTER;
-        for (int l = 0; l < L; ++l)
-            if (!t.maps[l]) return BXI_ERR_NULL_POINTER;
-    }
-    if (grad_kernel_maps)
-        for (int l = 0; l < L; ++l) {
-            if (!grad_kernel_maps[l]) return BXI_ERR_NULL_POINTER;
-            t.gmaps[l] = static_cast<float*>(grad_kernel_maps[l]);
-        }
+    rc = dconv_backward_args(t, N, feat, out, grad_out, status, cells, grad_kernel_maps);
+    if (rc != BXI_OK) return rc;
     Dconv16Space sp = {nullptr, nullptr, nullptr, 0};
     hipStream_t s = as_stream(stream);
     if (N > 0) {
         if (!workspace_ok(workspace, workspace_bytes, bxi_solo_dconv16_backward_workspace_bytes(N, B, E, H, W), 16)) return BXI_ERR_WORKSPACE;
         dconv16_workspace(N, B, E, H, W, true, workspace, &sp);
-        BXI_LAUNCH("solo_dconv16_gather", s, dconv16_gather_kernel<true>, dim3((unsigned)sp.slots, 4), dim3(kDcThreads), 0, s, t, cells, sp.kT, status, E);
-        rc = check_launch();
+        rc = dconv_gather<h16, Kr16>("solo_dconv16_gather", t, cells, sp, status, E, s);
         if (rc != BXI_OK) return rc;
     }
     // without gradient maps the feature is not read and the partial sums are not formed
@@ -458,18 +391,9 @@ extern "C" int bxi_solo_dconv16_backward(const void* feat, int dtype, int B, int
                   : dconv16_backward_launch<false, false>(t, f, sp, out, grad_out, gf, part, E, HW, N, activation, s);
     if (rc != BXI_OK || !grad_kernel_maps) return rc;
     if (part) {
-        BXI_LAUNCH("solo_dconv16_reduce", s, dconv_reduce_kernel, dim3((unsigned)N, (unsigned)((E + 31) / 32)), dim3(32 * kDcReduceLanes), 0, s, part, sp.gk,
-                   E, tiles, N);
-        rc = check_launch();
+        rc = dconv_reduce("solo_dconv16_reduce", part, sp.gk, E, tiles, N, s);
         if (rc != BXI_OK) return rc;
     }
-    int64_t most = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t total = (int64_t)(layout == BXI_DCONV_ROWS ? 1 : B) * E * t.cells[l];
-        most = total > most ? total : most;
-    }
-    const dim3 grid((unsigned)((most + kDcThreads - 1) / kDcThreads), (unsigned)L);
-    if (bf) BXI_LAUNCH("solo_dconv16_scatter", s, dconv16_scatter_kernel<true>, grid, dim3(kDcThreads), 0, s, t, cells, sp.gk, E);
-    else BXI_LAUNCH("solo_dconv16_scatter", s, dconv16_scatter_kernel<false>, grid, dim3(kDcThreads), 0, s, t, cells, sp.gk, E);
-    return check_launch();
+    return bf ? dconv_scatter<h16, true>("solo_dconv16_scatter", t, cells, sp.gk, E, s)
+              : dconv_scatter<h16, false>("solo_dconv16_scatter", t, cells, sp.gk, E, s);
 }

@@ -6,7 +6,8 @@
 // of one output size), and the product of solo_dconv.hip -- its gather, its MFMA walk, its per-tile partial sums, its pass over every map
 // element -- runs on the resized feature for the group's levels through that family's own entry points: the rows of a group are
 // contiguous (level-major), so a group is a sub-range of the maps, the counts, the cells and the output.  At ratios 2 and 4 the product
-// runs over a quarter and a sixteenth of the pixels.  New here:
+// runs over a quarter and a sixteenth of the pixels.  From solo_dconv_device.hpp this file takes only the constants; what lives here is
+// the size-group plan (dconvl_plan), the two entry points and three kernels:
 //
 // dconvl_resize_kernel   one thread per (image, channel, output pixel) of a resampled group: torch's bilinear weights for a given size
 //   (taps_of), the four taps in torch's order.  An image without rows in the group returns before it reads anything, and nothing reads
@@ -15,6 +16,8 @@
 //   group's feature gradient (written once to the workspace by the product's backward, zeros for an image without rows).  For a source
 //   pixel it visits the output pixels whose taps name it, rows then columns ascending, found with the forward's own taps_of over a
 //   range that cannot miss one.  No atomics, every element written.
+// dconvl_zero_kernel     (dconvl_zero) every element of a gradient that no row reaches: all of them when N == 0, the maps of a group
+//   without rows otherwise.
 #include "solo_dconv_device.hpp"
 
 #include "../../include/boxinst/boxinst_hip_dconvl.h"
@@ -109,6 +112,11 @@ __global__ void __launch_bounds__(kDcThreads) dconvl_adjoint_kernel(const AdjGro
 __global__ void __launch_bounds__(kDcThreads) dconvl_zero_kernel(float* __restrict__ dst, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * kDcThreads + threadIdx.x;
     if (i < n) dst[i] = 0.f;
+}
+static int dconvl_zero(void* dst, int64_t n, hipStream_t s) {
+    BXI_LAUNCH("solo_dconvl_zero", s, dconvl_zero_kernel, dim3((unsigned)((n + kDcThreads - 1) / kDcThreads)), dim3(kDcThreads), 0, s,
+               static_cast<float*>(dst), n);
+    return check_launch();
 }
 
 // a run of consecutive levels of one output size
@@ -260,16 +268,11 @@ extern "C" int bxi_solo_dconvl_backward_f32(const float* feat, int B, int E, int
     hipStream_t s = as_stream(stream);
     if (N == 0) {                                                    // all-zero gradients, nothing else
         if (grad_feat) {
-            const int64_t n = (int64_t)B * E * H * W;
-            BXI_LAUNCH("solo_dconvl_zero", s, dconvl_zero_kernel, dim3((unsigned)((n + kDcThreads - 1) / kDcThreads)), dim3(kDcThreads), 0, s, grad_feat, n);
-            rc = check_launch();
+            rc = dconvl_zero(grad_feat, (int64_t)B * E * H * W, s);
             if (rc != BXI_OK) return rc;
         }
         for (int l = 0; grad_kernel_maps && l < L; ++l) {
-            const int64_t n = (int64_t)B * E * grids[l] * grids[l];
-            BXI_LAUNCH("solo_dconvl_zero", s, dconvl_zero_kernel, dim3((unsigned)((n + kDcThreads - 1) / kDcThreads)), dim3(kDcThreads), 0, s,
-                       static_cast<float*>(grad_kernel_maps[l]), n);
-            rc = check_launch();
+            rc = dconvl_zero(grad_kernel_maps[l], (int64_t)B * E * grids[l] * grids[l], s);
             if (rc != BXI_OK) return rc;
         }
         return BXI_OK;
@@ -289,10 +292,7 @@ extern "C" int bxi_solo_dconvl_backward_f32(const float* feat, int B, int E, int
         void* const* gmaps = grad_kernel_maps ? grad_kernel_maps + g.l0 : nullptr;
         if (g.n == 0) {                                              // no row names a cell of these levels: their maps are zero
             for (int l = g.l0; gmaps && l < g.l0 + g.nl; ++l) {
-                const int64_t n = (int64_t)B * E * grids[l] * grids[l];
-                BXI_LAUNCH("solo_dconvl_zero", s, dconvl_zero_kernel, dim3((unsigned)((n + kDcThreads - 1) / kDcThreads)), dim3(kDcThreads), 0, s,
-                           static_cast<float*>(grad_kernel_maps[l]), n);
-                rc = check_launch();
+                rc = dconvl_zero(grad_kernel_maps[l], (int64_t)B * E * grids[l] * grids[l], s);
                 if (rc != BXI_OK) return rc;
             }
             continue;

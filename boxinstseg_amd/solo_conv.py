@@ -32,23 +32,61 @@ from ._common import current_stream, need_cuda
 __all__ = ['solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks']
 
 
+_HALF = {torch.float16: _lib.DCONV16_F16, torch.bfloat16: _lib.DCONV16_BF16}
+
+
+def _family(plan, feat):
+    """The entry points of the feature's precision: their common prefix, the suffix of the two calls, and what the half family's calls
+    take beyond the fp32 family's -- the dtype code after ``feat`` and the masks' dtype code after ``out`` / ``grad_out``."""
+    if feat.dtype in _HALF:
+        code = _HALF[feat.dtype]
+        return 'bxi_solo_dconv16', '', (code,), (_lib.DCONV16_OUT_F32 if plan.out_dtype == torch.float32 else code,)
+    return 'bxi_solo_dconv', '_f32', (), ()
+
+
 def _call_forward(plan, feat, maps):
     lib = _lib.load()
     dev = feat.device
     B, E, H, W = feat.shape
-    out = torch.empty((plan.N, H, W), dtype=torch.float32, device=dev)
+    fam, suffix, dtype_code, out_code = _family(plan, feat)
+    out = torch.empty((plan.N, H, W), dtype=plan.out_dtype, device=dev)
     img = torch.empty((plan.N,), dtype=torch.int64, device=dev)
-    ws_bytes = lib.bxi_solo_dconv_forward_workspace_bytes(plan.N, B, E)
+    ws_bytes = getattr(lib, fam + '_forward_workspace_bytes')(plan.N, B, E)
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    name = fam + '_forward' + suffix
     with torch.cuda.device(dev):
-        _lib.check('bxi_solo_dconv_forward_f32', lib.bxi_solo_dconv_forward_f32(
-            feat.data_ptr(), B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps), plan.layout,
-            None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(), img.data_ptr(),
-            plan.status.data_ptr(), ws.data_ptr(), ws_bytes, current_stream(dev)))
+        _lib.check(name, getattr(lib, name)(
+            feat.data_ptr(), *dtype_code, B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps),
+            plan.layout, None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(),
+            *out_code, img.data_ptr(), plan.status.data_ptr(), ws.data_ptr(), ws_bytes, current_stream(dev)))
     return out, img
 
 
+def _backward(ctx, g_out, g_dtype, feat, maps, ws_bytes, call):
+    """The backward of an autograd function over ``(plan, feat, *maps)``: which gradients are wanted, their buffers, the workspace of
+    ``ws_bytes(lib)`` bytes and the tuple autograd expects.  ``call(lib, g, g_feat, g_maps, ws, ws_bytes, stream)`` runs the library on
+    the pointers (None for a gradient nobody wants); box_solo_masks uses it too."""
+    need_feat, need_maps = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+    if not (need_feat or need_maps):
+        return (None, None) + (None,) * len(maps)
+    lib = _lib.load()
+    dev = feat.device
+    g = g_out.detach().to(g_dtype).contiguous()                            # autograd hands it over in the masks' dtype: no copy
+    g_feat = torch.empty_like(feat) if need_feat else None
+    g_maps = [torch.empty_like(m) for m in maps] if need_maps else None
+    nbytes = ws_bytes(lib)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        call(lib, g.data_ptr(), None if g_feat is None else g_feat.data_ptr(),
+             None if g_maps is None else _lib.ptr_array([m.data_ptr() for m in g_maps]), ws.data_ptr(), nbytes, current_stream(dev))
+    grads = [gm if need else None for gm, need in zip(g_maps, ctx.needs_input_grad[2:])] if need_maps else [None] * len(maps)
+    return (None, g_feat, *grads)
+
+
 class _DynamicMasks(torch.autograd.Function):
+    """Both precisions: fp32 tensors, or (``compute='half'``) the half tensors as they are, the masks in ``plan.out_dtype``, the gradients
+    in the inputs' dtype."""
+
     @staticmethod
     def forward(ctx, plan, feat, *maps):
         out, img = _call_forward(plan, feat, maps)
@@ -61,26 +99,18 @@ class _DynamicMasks(torch.autograd.Function):
     def backward(ctx, g_out, _g_img):
         plan = ctx.plan
         feat, out, *maps = ctx.saved_tensors
-        need_feat, need_maps = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        if not (need_feat or need_maps):
-            return (None, None) + (None,) * len(maps)
-        lib = _lib.load()
-        dev = feat.device
         B, E, H, W = feat.shape
-        g = g_out.detach().to(torch.float32).contiguous()
-        g_feat = torch.empty_like(feat) if need_feat else None
-        g_maps = [torch.empty_like(m) for m in maps] if need_maps else None
-        ws_bytes = lib.bxi_solo_dconv_backward_workspace_bytes(plan.N, B, E, H, W)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check('bxi_solo_dconv_backward_f32', lib.bxi_solo_dconv_backward_f32(
-                feat.data_ptr(), B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps), plan.layout,
-                None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(),
-                g.data_ptr(), None if g_feat is None else g_feat.data_ptr(),
-                None if g_maps is None else _lib.ptr_array([m.data_ptr() for m in g_maps]), plan.status.data_ptr(), ws.data_ptr(), ws_bytes,
-                current_stream(dev)))
-        grads = [gm if need else None for gm, need in zip(g_maps, ctx.needs_input_grad[2:])] if need_maps else [None] * len(maps)
-        return (None, g_feat, *grads)
+        fam, suffix, dtype_code, out_code = _family(plan, feat)
+        name = fam + '_backward' + suffix
+
+        def call(lib, g, g_feat, g_maps, ws, ws_bytes, stream):
+            _lib.check(name, getattr(lib, name)(
+                feat.data_ptr(), *dtype_code, B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps),
+                plan.layout, None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act,
+                out.data_ptr(), g, *out_code, g_feat, g_maps, plan.status.data_ptr(), ws, ws_bytes, stream))
+
+        return _backward(ctx, g_out, out.dtype, feat, maps,
+                         lambda lib: getattr(lib, fam + '_backward_workspace_bytes')(plan.N, B, E, H, W), call)
 
 
 def _fp32(t):
@@ -111,7 +141,7 @@ def _plan(kernel_preds_raw, grid_order, ins_pred, sigmoid, status):
     if status is None:
         status = torch.zeros(1, dtype=torch.int32, device=ins_pred.device)
     return types.SimpleNamespace(layout=_lib.DCONV_MAPS, grids=[int(m.shape[2]) for m in maps], counts=counts, cells=cells, N=N,
-                                 act=_lib.DCONV_SIGMOID if sigmoid else _lib.DCONV_NONE, status=status, L=L, B=B)
+                                 act=_lib.DCONV_SIGMOID if sigmoid else _lib.DCONV_NONE, status=status, L=L, B=B, out_dtype=torch.float32)
 
 
 def _lists(plan, out, img):
@@ -126,15 +156,12 @@ def _lists(plan, out, img):
 
 
 def _run(plan, kernel_preds_raw, ins_pred, compute='fp32', out_dtype=None):
-    if compute == 'half':
+    if compute == 'half':                                                  # the tensors as they are; fp32 plans keep their fp32 masks
         plan.out_dtype = out_dtype or ins_pred.dtype
-        out, img = _DynamicMasks16.apply(plan, ins_pred.contiguous(), *[m.contiguous() for m in kernel_preds_raw])
+        out, img = _DynamicMasks.apply(plan, ins_pred.contiguous(), *[m.contiguous() for m in kernel_preds_raw])
     else:
         out, img = _DynamicMasks.apply(plan, _fp32(ins_pred), *[_fp32(m) for m in kernel_preds_raw])
     return _lists(plan, out, img)
-
-
-_HALF = {torch.float16: _lib.DCONV16_F16, torch.bfloat16: _lib.DCONV16_BF16}
 
 
 def _check_compute(compute, out_dtype, **tensors):
@@ -153,63 +180,6 @@ def _check_compute(compute, out_dtype, **tensors):
                            + ', '.join(f'{n} {d}' for n, d in dtypes.items()))
     if out_dtype not in (None, first, torch.float32):
         raise RuntimeError(f"compute='half' returns masks in the inputs' dtype {first} or in torch.float32, got out_dtype={out_dtype}")
-
-
-def _out_code(plan, dtype):
-    return _lib.DCONV16_OUT_F32 if plan.out_dtype == torch.float32 else _HALF[dtype]
-
-
-def _call_forward16(plan, feat, maps):
-    lib = _lib.load()
-    dev = feat.device
-    B, E, H, W = feat.shape
-    out = torch.empty((plan.N, H, W), dtype=plan.out_dtype, device=dev)
-    img = torch.empty((plan.N,), dtype=torch.int64, device=dev)
-    ws_bytes = lib.bxi_solo_dconv16_forward_workspace_bytes(plan.N, B, E)
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check('bxi_solo_dconv16_forward', lib.bxi_solo_dconv16_forward(
-            feat.data_ptr(), _HALF[feat.dtype], B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps),
-            plan.layout, None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act, out.data_ptr(),
-            _out_code(plan, feat.dtype), img.data_ptr(), plan.status.data_ptr(), ws.data_ptr(), ws_bytes, current_stream(dev)))
-    return out, img
-
-
-class _DynamicMasks16(torch.autograd.Function):
-    """``compute='half'``: the tensors as they are, the masks in ``plan.out_dtype``, the gradients in the inputs' dtype."""
-
-    @staticmethod
-    def forward(ctx, plan, feat, *maps):
-        out, img = _call_forward16(plan, feat, maps)
-        ctx.plan = plan
-        ctx.save_for_backward(feat, out, *maps)
-        ctx.mark_non_differentiable(img)
-        return out, img
-
-    @staticmethod
-    def backward(ctx, g_out, _g_img):
-        plan = ctx.plan
-        feat, out, *maps = ctx.saved_tensors
-        need_feat, need_maps = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        if not (need_feat or need_maps):
-            return (None, None) + (None,) * len(maps)
-        lib = _lib.load()
-        dev = feat.device
-        B, E, H, W = feat.shape
-        g = g_out.detach().to(out.dtype).contiguous()                      # autograd hands it over in the masks' dtype: no copy
-        g_feat = torch.empty_like(feat) if need_feat else None
-        g_maps = [torch.empty_like(m) for m in maps] if need_maps else None
-        ws_bytes = lib.bxi_solo_dconv16_backward_workspace_bytes(plan.N, B, E, H, W)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check('bxi_solo_dconv16_backward', lib.bxi_solo_dconv16_backward(
-                feat.data_ptr(), _HALF[feat.dtype], B, E, H, W, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids),
-                len(maps), plan.layout, None if plan.cells is None else plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act,
-                out.data_ptr(), g.data_ptr(), _out_code(plan, feat.dtype), None if g_feat is None else g_feat.data_ptr(),
-                None if g_maps is None else _lib.ptr_array([m.data_ptr() for m in g_maps]), plan.status.data_ptr(), ws.data_ptr(), ws_bytes,
-                current_stream(dev)))
-        grads = [gm if need else None for gm, need in zip(g_maps, ctx.needs_input_grad[2:])] if need_maps else [None] * len(maps)
-        return (None, g_feat, *grads)
 
 
 def solo_dynamic_masks(kernel_preds_raw, grid_order, ins_pred, sigmoid=True, status=None, compute='fp32', out_dtype=None):
@@ -263,9 +233,8 @@ def solo_candidate_masks(seg_pred, kernel_preds, rows=None, sigmoid=True, status
         status = torch.zeros(1, dtype=torch.int32, device=seg_pred.device)
     plan = types.SimpleNamespace(layout=_lib.DCONV_ROWS, grids=[max(int(kernel_preds.shape[0]), 1)], counts=[n], N=n,
                                  cells=None if rows is None else rows.contiguous(), act=_lib.DCONV_SIGMOID if sigmoid else _lib.DCONV_NONE,
-                                 status=status, L=1, B=1)
+                                 status=status, L=1, B=1, out_dtype=torch.float32)
     if compute == 'half':
         plan.out_dtype = out_dtype or seg_pred.dtype
-        return _call_forward16(plan, seg_pred.detach().contiguous(), [kernel_preds.detach().contiguous()])[0]
-    out, _ = _call_forward(plan, _fp32(seg_pred.detach()), [_fp32(kernel_preds.detach())])
-    return out
+        return _call_forward(plan, seg_pred.detach().contiguous(), [kernel_preds.detach().contiguous()])[0]
+    return _call_forward(plan, _fp32(seg_pred.detach()), [_fp32(kernel_preds.detach())])[0]

@@ -255,7 +255,7 @@ def test_a_cell_outside_its_map_and_no_rows_at_all(dev, dtype):
     plan = SC._plan(maps, order, feat, True, None)
     plan.out_dtype = dtype
     with G.poisoned_empty():
-        out, _ = SC._DynamicMasks16.apply(plan, feat, *maps)
+        out, _ = SC._DynamicMasks.apply(plan, feat, *maps)
         assert out.shape == (0, 7, 9) and out.dtype == dtype
         out.sum().backward()
     assert feat.grad.dtype == dtype and not bool(feat.grad.any()) and not any(bool(m.grad.any()) for m in maps)

@@ -111,7 +111,7 @@ def abi_calls(feat, maps, order, g):
     plan = SC._plan(maps, order, feat, True, None)
     plan.out_dtype = feat.dtype
     code = SC._HALF[feat.dtype]
-    out, img = SC._call_forward16(plan, feat, maps)
+    out, img = SC._call_forward(plan, feat, maps)
     head = (feat.data_ptr(), code, B, E, *HW, _lib.ptr_array([m.data_ptr() for m in maps]), _lib.int_array(plan.grids), len(maps), plan.layout,
             plan.cells.data_ptr(), _lib.int_array(plan.counts), plan.N, plan.act)
     gf, gm = torch.empty_like(feat), [torch.empty_like(m) for m in maps]
@@ -141,9 +141,9 @@ def traced(path):
     if path and os.path.exists(path):
         with open(path) as fh:
             for row in csv.DictReader(fh):
-                for key in ('dconv16_gather_kernel', 'dconv16_fwd_kernel', 'dconv16_bwd_kernel', 'dconv_reduce_kernel', 'dconv16_scatter_kernel'):
+                for key in ('dconv_gather_kernel', 'dconv16_fwd_kernel', 'dconv16_bwd_kernel', 'dconv_reduce_kernel', 'dconv_scatter_kernel'):
                     if key in row['Name']:
-                        form = '<true>' if 'gather_kernel<true>' in row['Name'] else '<false>' if 'gather_kernel<false>' in row['Name'] else ''
+                        form = '<Kr16>' if 'Kr16>' in row['Name'] else '<Kt16>' if 'Kt16>' in row['Name'] else ''      # the gather's layout tag
                         out[key + form] = round(float(row['AverageNs']) / 1e3, 2)
     return out
 
