@@ -52,6 +52,10 @@ Public surface (mirrors the reference's for this path):
     box2mask_instances                 <-> Box2Mask after the decoder: both F.interpolate, crop, ``> 0``, mask score, mask2bbox (no fp32 canvas)
     MaskFormerFusionHead               <-> mmdet's panoptic_fusion_head of configs/box2mask (instance results; registered in HEADS)
     box2mask_format_results            <-> the formatting loop of MaskFormer.simple_test (bbox2result, masks to numpy: one host copy, one sync)
+    rle_encode, EncodedMasks           <-> pycocotools.mask.encode of every mask of a [n,h,w] block, on the GPU (restated format, unpinned; four launches)
+    rle_decode                         <-> pycocotools.mask.decode on the host in numpy (for users and tests)
+    solo_encode_results                <-> format_results + encode_mask_results for the SOLOv2-style heads: RLE dicts instead of masks cross to the host
+    box2mask_encode_results            <-> MaskFormer.simple_test's formatting + encode_mask_results for Box2Mask, the same way
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -74,6 +78,7 @@ from .solo_conv import solo_candidate_masks, solo_dynamic_masks, solo_dynamic_ma
 from .box_solo_masks import box_solov2_get_seg_single_kernels, box_solov2_ins_preds, box_solov2_set_cells
 from .masked_attn import MultiheadAttention, PackedAttnMask, attn_mask_bits, box2mask_attn_mask, masked_attention, pack_attn_mask
 from .inst_post import MaskFormerFusionHead, box2mask_format_results, box2mask_instances, instance_topk
+from .mask_rle import EncodedMasks, box2mask_encode_results, rle_decode, rle_encode, solo_encode_results
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -94,5 +99,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'solo_dynamic_masks', 'solo_dynamic_masks_pair', 'solo_candidate_masks',
            'box_solov2_ins_preds', 'box_solov2_set_cells', 'box_solov2_get_seg_single_kernels',
            'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention',
-           'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results']
+           'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results',
+           'rle_encode', 'rle_decode', 'EncodedMasks', 'solo_encode_results', 'box2mask_encode_results']
 __version__ = '0.1.0'

@@ -373,6 +373,20 @@ LEVEL_FAMILIES = [
     ('dconvl', ('include/boxinst/boxinst_hip_dconvl.h',), DCONVL_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_rle.h (the test-time masks as COCO run-length encodings: counts and strings of every mask, packed)
+RLE_STATUS_OVER_RUNS, RLE_STATUS_OVER_CHARS, RLE_MAX_PIXELS, RLE_MAX_CHARS_PER_COUNT = 1, 2, 1 << 29, 6
+RLE_SIGNATURES = {
+    'bxi_mask_rle_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'bxi_mask_rle_u8': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
+}
+
+# what the test pipelines end in: a fifth list, because tests/test_abi_family_dconvl.py pins LEVEL_FAMILIES to ['dconvl']; the same
+# triples, applied by load() behind the other four with the same check across all lists (tests/test_abi_family_rle.py)
+RESULT_FAMILIES = [
+    ('rle', ('include/boxinst/boxinst_hip_rle.h',), RLE_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -394,7 +408,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')
