@@ -129,7 +129,10 @@ def test_cate_loss_and_gradient(dev, name, mode):
 
 @pytest.mark.parametrize('mode', R.MODES)
 def test_seventy_instances_against_the_restatement(dev, mode):
-    """More instances than a wave has lanes, one image on a 128 x 160 canvas (moments stay below 2^24)."""
+    """More instances than a wave has lanes, one image on a 128 x 160 canvas.  The moments stay below 2^24 because that is where the
+    reference's own fp32 sums stop being exact, not because the library needs it: its moments are exact integers, rounded once.
+    Masks whose sums leave 2^24 and 2^32 are checked under that rule, against closed forms, in part C of
+    tests/test_gpu_solo_targets_edges.py, and moments no fp32 holds go through the assignment in its large-moment plant."""
     import boxinstseg_amd as B
     boxes, labels, masks = R.random_case(70, 70, 128, 160, 7)
     kw = dict(num_grids=[12, 10, 8, 6, 4], scale_ranges=[(1, 14), (7, 24), (12, 32), (20, 48), (32, 256)], sigma=0.2, num_classes=7)
