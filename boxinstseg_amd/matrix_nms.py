@@ -82,6 +82,10 @@ def matrix_nms_decay(bits, area, labels, order, scores_sorted, hw, kernel='gauss
         raise RuntimeError(f'bits must be contiguous int64 [n_all, {_words(h, w)}] for {h}x{w} masks, got {bits.dtype} {tuple(bits.shape)}')
     if area.numel() != n_all or labels.numel() != n_all or scores_sorted.numel() != n:
         raise RuntimeError(f'area / labels must have {n_all} entries and scores_sorted {n}')
+    if n > _lib.NMS_MAX_CANDIDATES:              # said here, before the n x n allocation; the entry point refuses the same with BXI_ERR_UNSUPPORTED
+        raise NotImplementedError(f'{n} candidates would enter the n x n stage of Matrix NMS: at most BXI_NMS_MAX_CANDIDATES = '
+                                  f'{_lib.NMS_MAX_CANDIDATES} are supported (include/boxinst/boxinst_hip_post.h); cut them with '
+                                  f'nms_pre <= {_lib.NMS_MAX_CANDIDATES}')
     area = area.to(torch.int32).contiguous()
     labels = labels.to(torch.int64).contiguous()
     order = order.to(torch.int64).contiguous()

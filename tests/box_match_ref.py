@@ -19,8 +19,26 @@ CASES = {
     'wide': (14, (5, 70), (20, 280), 5, (5,), 'defaults', 5),       # a row longer than a wave, H + W = 300
     'empty': (15, (7, 9), (20, 30), 5, (0,), 'cfg', 4),             # no ground truth
     'batch': (16, (13, 11), (52, 44), 12, (0, 4, 7), 'cfg', 5),     # three problems, one of them empty
+    # class rows and label lists longer than a wave (the shipped COCO config has 81 columns), the solver past 64 rows in both orientations
+    'coco': (17, (7, 9), (28, 36), 100, (70, 1), 'cfg', 80),        # 81 columns and 70 labels: two trips each; solver transposed, 70 x 100
+    'crowd': (18, (7, 9), (28, 36), 70, (100,), 'cfg', 63),         # exactly 64 columns; solver NOT transposed, 70 rows x 100 columns
+    'c65': (19, (7, 9), (14, 18), 5, (3,), 'defaults', 64),         # 65 columns: a one-element second trip
 }
 PARAMS = {'cfg': CFG, 'defaults': DEFAULTS}
+
+
+LIMIT_SIDE = 1024                                                   # BXI_MATCH_MAX_SIDE: matrices of this size are built, not stored
+
+
+def limit_uniform(Q, G):
+    """The uniform fp32 cost of the solver's limit cases; the fixture pins the square one by a CRC32 of its bytes."""
+    return np.random.default_rng(0).uniform(0, 10, (Q, G)).astype(np.float32)
+
+
+def limit_ties(Q=LIMIT_SIDE, G=LIMIT_SIDE):
+    """Exact small integers (0..1008) as fp32 with many optimal assignments."""
+    i, j = np.arange(Q, dtype=np.int64)[:, None], np.arange(G, dtype=np.int64)[None, :]
+    return ((i * 7919 + j * 104729 + i * j * 31 + i * i * 17 + j * j * 13) % 1009).astype(np.float32)
 
 
 def make_inputs(name):
@@ -101,8 +119,10 @@ def bin_dice(p, t, eps):
     return 1.0 - (num + eps) / (den + eps)
 
 
-def class_cost(cls, labels, weight):
-    z = np.asarray(cls, np.float64)
+def class_cost(cls, labels, weight, dtype=np.float64):
+    """``dtype=np.float32``: the same statement in fp32 arithmetic, for a measured fp32-against-fp64 difference (bin_dice stays in the
+    precision of its arguments)."""
+    z = np.asarray(cls, dtype)
     e = np.exp(z - z.max(axis=1, keepdims=True))
     return -(e / e.sum(axis=1, keepdims=True))[:, labels] * weight
 

@@ -11,13 +11,16 @@ cost has to be within 4 x tol of the fp64 cost.  The generator asserts that ever
 in turn, the best other assignment costs more than the optimum by over 100 x tol -- otherwise the seed is rejected.
 
 ``lsa_*``: cost matrices for the solver alone.  ``rand``: uniform fp32 (unique optimum, separated the same way); ``ties``: small
-integers, where many assignments share the optimal total and only the total is stored as the expectation.
+integers, where many assignments share the optimal total and only the total is stored as the expectation.  ``lsa_limit_*``: the
+1024 x 1024 matrices of tests/box_match_ref.py (limit_uniform, limit_ties) are too large to store and are rebuilt by the test; stored
+are a CRC32 of the uniform matrix's bytes, scipy's column indices on it (int16) and scipy's total on the tied one.
 """
 import ast
 import contextlib
 import os
 import sys
 import types
+import zlib
 
 import numpy as np
 import torch
@@ -35,8 +38,12 @@ ASSIGNER_FILE = os.path.join(REF, 'mmdet/core/bbox/assigners/mask_hungarian_assi
 HEAD_FILE = os.path.join(REF, 'mmdet/models/dense_heads/box2mask_head.py')
 CONFIG_FILE = os.path.join(REF, 'configs/box2mask/box2mask_r50_lsj_8x2_50e_coco.py')
 
-LSA_RAND = ((67, 7), (5, 5), (3, 5), (100, 23), (64, 64), (1, 1), (1, 4), (130, 70))
-LSA_TIES = ((20, 9), (6, 6), (4, 9), (64, 40))
+# the first LSA_STREAM[0] / LSA_STREAM[1] matrices come from one shared stream (rand, then ties); every later one has a stream of its
+# own, so that an addition never moves an earlier matrix.  (100, 120): not transposed with both sides above a wave; (65, 65), (65, 64),
+# (64, 65): one past a wave in each orientation
+LSA_RAND = ((67, 7), (5, 5), (3, 5), (100, 23), (64, 64), (1, 1), (1, 4), (130, 70), (100, 120), (65, 65), (65, 64), (64, 65))
+LSA_TIES = ((20, 9), (6, 6), (4, 9), (64, 40), (100, 120))
+LSA_STREAM = (8, 4)
 SEPARATION = 100.0
 
 
@@ -181,8 +188,9 @@ def main():
                   f'next best assignment +{gap:.3e} ({gap / tol if tol else np.inf:.0f} x tol)')
             assert gap > SEPARATION * tol, 'the optimum is not separated: pick another seed'
         out.update(case)
-    rng = np.random.default_rng(2024)
+    shared = np.random.default_rng(2024)
     for n, (Q, G) in enumerate(LSA_RAND):
+        rng = shared if n < LSA_STREAM[0] else np.random.default_rng([2024, 0, n])
         c = rng.uniform(0, 10, (Q, G)).astype(np.float32)
         rows, cols = linear_sum_assignment(c)
         gap = separation(c, rows, cols)
@@ -190,10 +198,23 @@ def main():
         assert gap > 1e-4
         out.update({f'lsa_rand{n}_cost': c, f'lsa_rand{n}_rows': rows.astype(np.int64), f'lsa_rand{n}_cols': cols.astype(np.int64)})
     for n, (Q, G) in enumerate(LSA_TIES):
+        rng = shared if n < LSA_STREAM[1] else np.random.default_rng([2024, 1, n])
         c = rng.integers(1, 6, (Q, G)).astype(np.int8)
         rows, cols = linear_sum_assignment(c)
         print(f'lsa_ties{n}: {Q}x{G} optimal total {int(c[rows, cols].sum())}')
         out.update({f'lsa_ties{n}_cost': c, f'lsa_ties{n}_total': np.array(int(c[rows, cols].sum()))})
+    side = R.LIMIT_SIDE
+    c = R.limit_uniform(side, side)
+    rows, cols = linear_sum_assignment(c)
+    assert np.array_equal(rows, np.arange(side)) and np.array_equal(R.linear_sum_assignment(c)[1], cols), 'the restatement is not scipy here'
+    out.update({'lsa_limit_crc': np.array(zlib.crc32(c.tobytes()), np.uint32), 'lsa_limit_cols': cols.astype(np.int16)})
+    t = R.limit_ties()
+    rows, cols = linear_sum_assignment(t)
+    total = int(t[rows, cols].astype(np.int64).sum())
+    rr, rc = R.linear_sum_assignment(t)
+    assert int(t[rr, rc].astype(np.int64).sum()) == total
+    out['lsa_limit_ties_total'] = np.array(total)
+    print(f'lsa_limit: uniform {side}x{side} crc {int(out["lsa_limit_crc"]):#010x}, ties optimal total {total}')
     path = os.path.join(HERE, 'box_match.npz')
     np.savez_compressed(path, **out)
     with open(os.path.join(HERE, 'box_match_assigner_cfg.json'), 'w') as fh:      # constants only: the config block as data

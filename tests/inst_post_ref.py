@@ -2,6 +2,7 @@
 tests/test_gpu_inst_post.py, tests/test_gpu_guarded_inst.py, the fixture generator and tools/inst_post_bench.py.
 
     softmax64(mask_cls)                  F.softmax(mask_cls, -1)[..., :-1] in float64 (maskformer_fusion_head.py:136)
+    softmax_error_bound(mask_cls)        the derived bound of the kernel's fp32 scores against softmax64 (rows of any length)
     topk_ref(mask_cls, things, k)        :133-151 with the library's DEFINED order: descending score, equal scores by ascending flat index
                                          q * C + c, NaN last; then the is_thing filter -> (scores, labels, query, flat) of the kept rows
     p64(logits, query, up, crop, out)    box2mask_head.py:452-457 and maskformer_fusion_head.py:211-221 in float64: the two-stage composition
@@ -63,6 +64,26 @@ def softmax64(mask_cls):
     with np.errstate(invalid='ignore', over='ignore'):
         e = np.exp(x - np.max(np.where(np.isnan(x), -np.inf, x), -1, keepdims=True))
         return (e / e.sum(-1, keepdims=True))[..., :-1]
+
+
+def softmax_error_bound(mask_cls):
+    """An upper bound of |inst_topk_kernel's fp32 score - softmax64|, element by element, from the kernel's stated arithmetic and
+    nothing measured.  With e = 2^-24, d_c = max - x_c >= 0 and p the float64 softmax over all C + 1 columns:
+      * the argument x_c - max is one fp32 subtraction, off by at most e d_c, which is a RELATIVE error e d_c of its exponential;
+        expf is within one ulp, at most 2 e relative: a term is off by at most (d_c + 2) e;
+      * the denominator inherits the terms' errors weighted by their shares, A = sum_c p_c (d_c + 2), and adds its own roundings:
+        a lane adds its T = ceil((C + 1) / 64) terms one after the other (T - 1 roundings, the first addition is to zero), the wave total
+        is six tree levels, every rounding at most e of a partial sum of positive terms, hence of the total: (T - 1 + 6) e;
+      * one correctly rounded division: e.
+    Relative error of score c at first order: e ((d_c + 2) + A + (T + 5) + 1); the second-order terms are below 2^-38 relative and are
+    covered by counting expf at its worst-case ulp.  Returns the absolute bound without the background column, like softmax64."""
+    x = np.asarray(mask_cls, np.float64)
+    d = x.max(-1, keepdims=True) - x
+    e = np.exp(-d)
+    p = e / e.sum(-1, keepdims=True)
+    terms = -(-x.shape[-1] // 64)
+    rel = 2.0 ** -24 * ((d + 2) + (p * (d + 2)).sum(-1, keepdims=True) + (terms + 5) + 1)
+    return (rel * p)[..., :-1]
 
 
 def defined_order(scores_flat):

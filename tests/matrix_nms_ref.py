@@ -41,7 +41,7 @@ def shuffled_scores(rng, n, lo=0.1, hi=0.95):
 def decay_iou_f32(flat, area, labels):
     """[n,P] bool (sorted), [n] counts, [n] labels -> the reference's ``iou_matrix * label_matrix`` in fp32 from integer counts."""
     n = len(flat)
-    x = flat.astype(np.int64)
+    x = flat.astype(np.float64)                  # 0 / 1: the products and their sums (below 2^24) are exact integers, and this is a BLAS call
     inter = (x @ x.T).astype(f32)
     a = np.asarray(area).astype(f32)
     with np.errstate(invalid='ignore', divide='ignore'):

@@ -25,10 +25,10 @@ QUERY = [4, 0, -1, 2, 2, 5]                                  # a repeat and two 
 
 
 @pytest.mark.parametrize('lead', [1, 2, 3])
-def test_inst_topk_guarded(dev, lead):
+def test_inst_topk_guarded(dev, lead, B=2, Q=12, things=3, stuff=2, k=14):
+    """(the shape arguments have defaults, so they are no fixtures: test_inst_topk_guarded_largest_launch passes its own)"""
     from boxinstseg_amd import _lib
     lib = _lib.load()
-    B, Q, things, stuff, k = 2, 12, 3, 2, 14
     C = things + stuff
     cls = torch.from_numpy(np.random.default_rng(3).normal(0, 2, (B, Q, C + 1)).astype(np.float32)).to(dev)
     want = [torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int64, device=dev),
@@ -45,9 +45,15 @@ def test_inst_topk_guarded(dev, lead):
     for g, w in zip((gs, gl, gq, gn), want):
         assert G.same(g.t, w)
     counts = want[3].tolist()
-    assert all(0 < c < k for c in counts)                                      # some stuff entries were dropped in both images
+    assert all(0 < c < k for c in counts) if stuff else counts == [k] * B      # some stuff entries were dropped in every image
     for b, c in enumerate(counts):
         assert want[1][b, c:].tolist() == [-1] * (k - c) and want[2][b, c:].tolist() == [-1] * (k - c) and want[0][b, c:].tolist() == [0.0] * (k - c)
+
+
+@pytest.mark.parametrize('lead', [1, 2, 3])
+def test_inst_topk_guarded_largest_launch(dev, lead):
+    """16384 keys (128 KiB of LDS), as many output rows written in 16 rounds, rows of 257 logits: nothing is filtered, count = k."""
+    test_inst_topk_guarded(dev, lead, B=1, Q=64, things=256, stuff=0, k=16384)
 
 
 @pytest.mark.parametrize('out_w', [64, 61])

@@ -7,7 +7,8 @@ Rules (conditions on the inputs, asserted at the top of each test, not measureme
 * the top-k: every index with s64 > cut (1 + 2^-20) is selected, none with s64 < cut (1 - 2^-20), cut = the k-th largest float64 score;
   the band around the cut holds at most two indices beyond the planted ties;
 * scores are within max(4 |ref32 - ref64|, 4 x 2^-24 |ref64|) (class scores) and max(4 |ref32 - ref64|, 8 x 2^-24 |ref64|) (mask and det
-  scores), ref32 being the reference's own fp32 arithmetic on the CPU;
+  scores), ref32 being the reference's own fp32 arithmetic on the CPU; the top-k cases that select deep into their rows are held to
+  the bound derived in tests/inst_post_ref.py (softmax_error_bound) instead, see TOPK_DERIVED_BOUND;
 * statistics and box corners are exactly what numpy counts on OUR mask bytes."""
 import types
 
@@ -139,10 +140,30 @@ def planted_cls(B, Q, C, k, seed):
     return np.stack(out), pairs
 
 
-@pytest.mark.parametrize('B,Q,things,stuff,k', [(2, 100, 80, 0, 100), (1, 7, 3, 0, 21), (2, 100, 60, 20, 100), (1, 7, 2, 1, 21)],
-                         ids=['coco', 'all', 'coco_stuff', 'all_stuff'])
-def test_topk(dev, B, Q, things, stuff, k):
+# id: (B, Q, things, stuff, k).  The sort size P is the power of two >= Q * (things + stuff); a row of more than 256 logits takes the
+# kernel's wide branch; the output is written in rounds of 1024.
+TOPK_CASES = {
+    'coco': (2, 100, 80, 0, 100), 'all': (1, 7, 3, 0, 21), 'coco_stuff': (2, 100, 60, 20, 100), 'all_stuff': (1, 7, 2, 1, 21),
+    'panoptic': (1, 100, 80, 53, 100),                   # N = 13300: P = 16384 (two blocks per wave, the last merge size), stuff filtered
+    'full_16384': (1, 64, 256, 0, 16384),                # N = P = 16384, no padding keys, 257 logits: the first wide row; k = N: 16 rounds
+    'last_register_row': (2, 64, 255, 0, 1025),          # 256 logits: the last row held in registers; N = 16320; k one past a round
+    'wide_rows': (1, 16, 1023, 0, 2500),                 # 1024 logits: 16 trips of the wide branch; N = 16368; k in its third round
+    'two_rounds_small': (1, 100, 80, 0, 2048),           # the 8192 sort, k exactly two rounds
+}
+# Cases whose scores are held to R.softmax_error_bound (derived there from the kernel's arithmetic) instead of the rule of the module
+# docstring.  That rule leans on torch's own fp32 softmax being off where the kernel is and has no term for the rounding of x - max,
+# a relative error of 2^-24 (max - x) in the score that both share: it fits selections near the top of their rows (k << N; the five
+# cases with k <= 1025 stay on it, at most 0.85 of it) and not deep ones, where max - x reaches 10 and more.  Measured on the rule of
+# the docstring, largest error / bound and entries above it: two_rounds_small 1.003 (1 of 2048), wide_rows 1.076 (1 of 2500),
+# full_16384 1.330 (33 of 16384), the largest relative errors 6.4, 6.6 and 10.5 x 2^-24; a CPU model of the kernel's order (numpy
+# fp32: lane sums, tree, division) gives 1.020, 1.078 and 1.349 on the same inputs.  On the derived bound: 0.37, 0.19 and 0.39.
+TOPK_DERIVED_BOUND = ('two_rounds_small', 'wide_rows', 'full_16384')
+
+
+@pytest.mark.parametrize('case', list(TOPK_CASES))
+def test_topk(dev, case):
     from boxinstseg_amd import instance_topk
+    B, Q, things, stuff, k = TOPK_CASES[case]
     C = things + stuff
     cls, pairs = planted_cls(B, Q, C, k, 17)
     s64 = R.softmax64(cls).reshape(B, -1)
@@ -187,7 +208,11 @@ def test_topk(dev, B, Q, things, stuff, k):
         # the scores
         tol = np.maximum(4 * np.abs(ref32[b][flat].astype(np.float64) - s64[b][flat]), 4 * EPS24 * s64[b][flat])
         err = np.abs(sc.astype(np.float64) - s64[b][flat])
-        print(f'topk B{b}: count {n}, score err / bound max {np.max(err / tol):.3f}')
+        derived = R.softmax_error_bound(cls[b]).reshape(-1)[flat]
+        print(f'topk {case} B{b}: count {n}, score err / bound max {np.max(err / tol):.3f} ({int((err > tol).sum())} above), '
+              f'err / derived bound max {np.max(err / derived):.3f}, err max {np.max(err / s64[b][flat]) / EPS24:.2f} x 2^-24 relative')
+        if case in TOPK_DERIVED_BOUND:
+            tol = derived
         assert np.all(err <= tol), (err / tol).max()
         if stuff:
             assert 0 < n < k or k == Q * C

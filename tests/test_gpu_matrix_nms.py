@@ -124,7 +124,11 @@ def run_stage(dev, masks, labels, scores, nms_pre=-1, kernel='gaussian', sigma=2
 STAGE_CASES = [(1, (7, 9), 'one'), (2, (24, 40), 'one'), (2, (25, 38), 'distinct'), (31, (25, 38), 'several'), (32, (50, 76), 'one'),
                (33, (7, 9), 'several'), (33, (24, 40), 'distinct'), (33, (25, 38), 'one'), (33, (50, 76), 'several'),
                (65, (24, 40), 'several'), (65, (7, 9), 'one'), (130, (25, 38), 'one'), (130, (50, 76), 'distinct'),
-               (130, (24, 40), 'several'), (300, (25, 38), 'several'), (300, (50, 76), 'one')]
+               (130, (24, 40), 'several'), (300, (25, 38), 'several'), (300, (50, 76), 'one'),
+               # past the 512 threads that fill the decay kernel's LDS tables: exactly one trip, one element of a second, a third, and
+               # BXI_NMS_MAX_CANDIDATES = 2048 (four full trips, a 16 MB matrix)
+               (512, (7, 9), 'several'), (513, (7, 9), 'one'), (1025, (24, 40), 'several'), (2048, (7, 9), 'several'),
+               (2048, (25, 38), 'one')]
 
 
 @pytest.mark.parametrize('n,hw,mode', STAGE_CASES)
@@ -170,7 +174,27 @@ def test_mask_matrix_nms_order_and_cuts_against_the_fixture(dev, name):
         assert_scores(s.cpu().numpy(), g[f'{name}_out_scores'], f'{name} scores vs the reference\'s fp32', rtol=RTOL + 1e-6)
 
 
-@pytest.mark.parametrize('n_all,nms_pre,hw', [(130, -1, (25, 38)), (300, -1, (50, 76)), (700, 500, (50, 76))])
+def test_more_candidates_than_the_limit_is_an_error_that_names_it(dev):
+    """2049 candidates and no nms_pre: an error that names the limit, never a truncated result; with nms_pre at the limit the same
+    candidates pass."""
+    from boxinstseg_amd import _lib, mask_matrix_nms
+    from boxinstseg_amd.matrix_nms import matrix_nms_scores, pack_masks
+    n_all = _lib.NMS_MAX_CANDIDATES + 1
+    assert n_all == 2049
+    rng = np.random.default_rng(n_all)
+    masks, labels, scores = _t(R.disc_masks(rng, n_all, 7, 9), dev), _t(rng.integers(0, 3, n_all), dev), _t(R.shuffled_scores(rng, n_all), dev)
+    for nms_pre in (-1, 0, n_all):
+        with pytest.raises(NotImplementedError, match=r'2049 candidates.*BXI_NMS_MAX_CANDIDATES = 2048.*nms_pre'):
+            mask_matrix_nms(masks, labels, scores, nms_pre=nms_pre)
+    bits, area = pack_masks(masks)
+    with pytest.raises(NotImplementedError, match='BXI_NMS_MAX_CANDIDATES = 2048'):
+        matrix_nms_scores(bits, area, labels, scores, (7, 9))
+    s, _, _, k = mask_matrix_nms(masks, labels, scores, nms_pre=n_all - 1)
+    assert len(k) == len(s) == n_all - 1 and int(scores.argmin()) not in k.cpu().tolist()
+
+
+@pytest.mark.parametrize('n_all,nms_pre,hw', [(130, -1, (25, 38)), (300, -1, (50, 76)), (700, 500, (50, 76)), (2048, -1, (7, 9)),
+                                              (2100, 2048, (7, 9))])
 def test_mask_matrix_nms_large_sets(dev, n_all, nms_pre, hw):
     """Near-ties are 1e-5 apart here: the set of keep_inds, the score of every index, and a non-increasing result."""
     from boxinstseg_amd import mask_matrix_nms

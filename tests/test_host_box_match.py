@@ -11,6 +11,7 @@ import importlib.util
 import json
 import os
 import re
+import zlib
 
 import numpy as np
 import pytest
@@ -24,7 +25,7 @@ CFG_JSON = os.path.join(ROOT, 'tests', 'golden', 'box_match_assigner_cfg.json')
 GENERATOR = os.path.join(ROOT, 'tests', 'golden', 'make_golden_box_match.py')
 HEADER = os.path.join(ROOT, 'include', 'boxinst', 'boxinst_hip_assign.h')
 REFERENCE = os.environ.get('BOXINST_REFERENCE_ROOT', '/root/reference')
-N_RAND, N_TIES = 8, 4
+N_RAND, N_TIES = 12, 5
 
 
 @pytest.fixture(scope='module', autouse=True)
@@ -91,6 +92,28 @@ def test_restatement_solver_on_the_stored_matrices():
     rows, cols = R.linear_sum_assignment(np.array([[1.0, 2.0], [1.5, 9.0]]))
     assert rows.tolist() == [0, 1] and cols.tolist() == [1, 0]
     assert not R.is_matching(np.array([0, 0]), np.array([0, 1]), 2, 2) and R.is_matching(np.array([1, 0]), np.array([0, 1]), 2, 2)
+
+
+def limit_uniform_pinned(g):
+    """The 1024 x 1024 uniform matrix and whether it is the one the generator saw (a numpy whose stream differs gives another)."""
+    c = R.limit_uniform(R.LIMIT_SIDE, R.LIMIT_SIDE)
+    return c, zlib.crc32(c.tobytes()) == int(g['lsa_limit_crc'])
+
+
+def test_restatement_solver_at_the_limit():
+    """The matrices of the GPU limit cases, built here as there: on the pinned uniform one the restatement's indices are scipy's stored
+    ones; on the tied one its total is scipy's."""
+    g = np.load(GOLDEN)
+    c, pinned = limit_uniform_pinned(g)
+    assert c.shape == (R.LIMIT_SIDE, R.LIMIT_SIDE) == (1024, 1024) and c.dtype == np.float32
+    rows, cols = R.linear_sum_assignment(c)
+    assert R.is_matching(rows, cols, *c.shape) and np.array_equal(rows, np.arange(R.LIMIT_SIDE))
+    if pinned:
+        assert g['lsa_limit_cols'].dtype == np.int16 and np.array_equal(cols, g['lsa_limit_cols'])
+    t = R.limit_ties()
+    assert t.dtype == np.float32 and np.array_equal(t, np.round(t)) and 0 <= t.min() and t.max() <= 1008
+    rows, cols = R.linear_sum_assignment(t)
+    assert R.is_matching(rows, cols, *t.shape) and int(t[rows, cols].astype(np.int64).sum()) == int(g['lsa_limit_ties_total']) == 1532
 
 
 @pytest.mark.parametrize('name', sorted(R.CASES))
