@@ -228,14 +228,17 @@ def det_img_dims(rescale=True):
     return [[float(s[0]), float(s[1])] + list(f) for s, f in zip(DET_IMG_SHAPES, DET_SCALES)]
 
 
-def det_inputs(seed):
+def det_inputs(seed, sizes=None, strides=None, B=None, extra_picks=None):
     """dict(cls, bbox, ctr, params: per level [B,K,H,W] float32).  Distances on a 1/8-pixel grid; image DET_EMPTY_IMAGE has no candidate;
-    the candidates' final scores are a shuffled linspace: pick the product, draw the centerness, solve for the class logit."""
+    the candidates' final scores are a shuffled linspace: pick the product, draw the centerness, solve for the class logit.
+    ``sizes`` / ``strides`` / ``B``: other levels and another batch (default: DET_SIZES, DET_STRIDES, DET_B -- the stored fixture);
+    ``extra_picks``: image -> [(level, y, x, class)] that become candidates as well, under the same shuffled linspace."""
     rng = np.random.default_rng(seed)
-    B, C, P = DET_B, DET_C, DET_P
+    sizes, strides = DET_SIZES if sizes is None else sizes, DET_STRIDES if strides is None else strides
+    B, C, P = DET_B if B is None else B, DET_C, DET_P
     logit = lambda p: np.log(p / (1 - p))                   # noqa: E731
     inp = dict(cls=[], bbox=[], ctr=[], params=[])
-    for (h, w), s in zip(DET_SIZES, DET_STRIDES):
+    for (h, w), s in zip(sizes, strides):
         inp['cls'].append(logit(0.01 * rng.uniform(0.7, 1.3, (B, C, h, w))))
         inp['ctr'].append(logit(rng.uniform(0.05, 0.95, (B, 1, h, w))))
         inp['bbox'].append(np.round(rng.uniform(0.5, 3.0, (B, 4, h, w)) * s * 8) / 8)
@@ -249,7 +252,7 @@ def det_inputs(seed):
             cx, cy = rng.uniform(30, 130), rng.uniform(20, 75)
             bw, bh = rng.uniform(24, 70), rng.uniform(20, 50)
             lab = int(rng.integers(0, C))
-            for lv, ((h, w), s) in enumerate(zip(DET_SIZES, DET_STRIDES)):
+            for lv, ((h, w), s) in enumerate(zip(sizes, strides)):
                 ys, xs = np.mgrid[0:h, 0:w]
                 px, py = (xs + 0.5) * s, (ys + 0.5) * s
                 inside = np.flatnonzero((np.abs(px - cx) < bw / 4) & (np.abs(py - cy) < bh / 4))
@@ -261,7 +264,7 @@ def det_inputs(seed):
                     picks.append((lv, y, x, lab))
                     if rng.uniform() < 0.25:
                         picks.append((lv, y, x, int((lab + 1 + rng.integers(0, C - 1)) % C)))
-        picks = sorted(set(picks))
+        picks = sorted(set(picks + list((extra_picks or {}).get(b, []))))
         prods = rng.permutation(np.linspace(0.06, 0.9, len(picks)))
         ctr_of = {}
         for (lv, y, x, lab), p in zip(picks, prods):
@@ -273,3 +276,47 @@ def det_inputs(seed):
                 inp['ctr'][lv][b, 0, y, x] = logit(ctr_of[key])
             inp['cls'][lv][b, lab, y, x] = logit(p / ctr_of[key])
     return {k: [np.ascontiguousarray(m.astype(F32)) for m in v] for k, v in inp.items()}
+
+
+# ---- the configs' level sizes: 20267 locations, 317 row tiles ---------------------------------------------------------------------
+EDGE_SIZES, EDGE_STRIDES, EDGE_B = ((100, 152), (50, 76), (25, 38), (13, 19), (7, 10)), (8, 16, 32, 64, 128), 2
+EDGE_IMG_SHAPES = ((800, 1216, 3), (768, 1184, 3))
+EDGE_SCALES = ((1.25, 1.5, 1.25, 1.5), (1.0, 1.0, 1.0, 1.0))
+EDGE_ROWS = (0, 63, 64, 16383, 16384, 16447, 16448, 20266)          # either side of a row tile's edge, of tile 256's, and the last row
+EDGE_CAPS = (256, 20)                                                # rows for every candidate, and fewer rows than candidates
+
+
+def edge_img_dims():
+    return [[float(s[0]), float(s[1])] + list(f) for s, f in zip(EDGE_IMG_SHAPES, EDGE_SCALES)]
+
+
+def edge_picks():
+    """(level, y, x, class) of the planted candidates of image 0: EDGE_ROWS, one more location in the middle of every level, and a second
+    class on the first and on the last row."""
+    off = level_offsets(EDGE_SIZES)
+    picks = []
+    for i, m in enumerate(EDGE_ROWS):
+        lv = int(np.searchsorted(off, m, side='right') - 1)
+        y, x = divmod(int(m - off[lv]), EDGE_SIZES[lv][1])
+        picks.append((lv, y, x, i % DET_C))
+    for lv, (h, w) in enumerate(EDGE_SIZES):
+        picks.append((lv, h // 2, w // 2, (lv + 2) % DET_C))
+    picks.append(picks[0][:3] + ((picks[0][3] + 1) % DET_C,))
+    picks.append(picks[len(EDGE_ROWS) - 1][:3] + ((picks[len(EDGE_ROWS) - 1][3] + 3) % DET_C,))
+    return picks
+
+
+def edge_inputs(seed):
+    """The recipe of det_inputs on EDGE_SIZES with B = 2: image 1 has no candidate, image 0 the recipe's own and edge_picks()."""
+    return det_inputs(seed, EDGE_SIZES, EDGE_STRIDES, EDGE_B, {0: edge_picks()})
+
+
+def edge_inputs_with_margin(seed, cfg, margin=1e-4):
+    """(seed, inputs) at the first seed from ``seed`` on whose candidates, of every location and of the per-level top ``cfg['nms_pre']``
+    alike (the score filter leaves the same ones), keep ``margin`` between every comparable IoU and the threshold in float64."""
+    for s in range(seed, seed + 50):
+        inp = edge_inputs(s)
+        c = candidates(inp, EDGE_STRIDES, edge_img_dims(), False, cfg['score_thr'], None, np.float64)[0]
+        if iou_margin(c['boxes'], c['labels'], cfg['iou_threshold']) > margin:
+            return s, inp
+    raise AssertionError('no seed with the IoU margin')

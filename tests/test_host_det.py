@@ -74,6 +74,62 @@ def test_restatement_reproduces_the_reference(name):
         assert [len(g[f'cut{b}_labels']) for b in (0, 2)] == [7, 7] and min(len(g[f'lv3{b}_labels']) for b in (0, 2)) > 7
 
 
+def test_default_recipe_ignores_the_new_parameters():
+    a, b = R.det_inputs(3), R.det_inputs(3, R.DET_SIZES, R.DET_STRIDES, R.DET_B, {})
+    assert all(np.array_equal(x, y) for k in a for x, y in zip(a[k], b[k]))
+
+
+EDGE_CFG = dict(nms_pre=1000, score_thr=0.05, iou_threshold=0.5, max_per_img=100, class_agnostic=False)
+
+
+def test_edge_recipe_reaches_the_late_tiles():
+    """The configs' level sizes: 20267 locations are 317 row tiles, more than one trip of the sum over the earlier tiles' counts."""
+    from boxinstseg_amd import _lib
+    tile, threads = _lib.DET_ROW_TILE, 4 * _lib.DET_ROW_TILE
+    off = R.level_offsets(R.EDGE_SIZES)
+    M_all = int(off[-1])
+    assert M_all == 20267 and (M_all + tile - 1) // tile == 317 and M_all - 316 * tile == 43 and R.EDGE_ROWS[-1] == M_all - 1
+    assert [m // tile for m in R.EDGE_ROWS] == [0, 0, 1, 255, 256, 256, 257, 316] and threads == 256
+    seed, inp = R.edge_inputs_with_margin(1, EDGE_CFG)
+    assert [m.shape for m in inp['cls']] == [(R.EDGE_B, R.DET_C, h, w) for h, w in R.EDGE_SIZES]
+    sel = R.select(inp, EDGE_CFG['nms_pre'], np.float64)
+    assert sel.shape == (R.EDGE_B, 3267) and (3267 + tile - 1) // tile == 52
+    # the cut of the top 1000 falls among the background's scores, far below every candidate's location
+    loc_score = R.location_scores(inp, np.float64)[0]
+    cand_locs = np.unique(R.candidates(inp, R.EDGE_STRIDES, R.edge_img_dims(), False, 0.05, None, np.float64)[0]['pos'])
+    for lv in range(2):
+        cut = np.sort(loc_score[off[lv]:off[lv + 1]])[::-1][EDGE_CFG['nms_pre'] - 1]
+        mine = cand_locs[(cand_locs >= off[lv]) & (cand_locs < off[lv + 1])]
+        assert len(mine) and loc_score[mine].min() > 2 * cut and set(mine.tolist()) <= set(sel[0].tolist())
+    pts, lvl = R.points_of(R.EDGE_SIZES, R.EDGE_STRIDES)
+    for name, rows in (('every location', None), ('the per-level top 1000', sel)):
+        for rescale in (False, True):
+            c64 = R.candidates(inp, R.EDGE_STRIDES, R.edge_img_dims(), rescale, 0.05, rows, np.float64)
+            c32 = R.candidates(inp, R.EDGE_STRIDES, R.edge_img_dims(), rescale, 0.05, rows, np.float32)
+            assert all(np.array_equal(a['pos'], b['pos']) and np.array_equal(a['labels'], b['labels']) for a, b in zip(c32, c64))
+        c = c64[0]
+        loc = c['pos'] if rows is None else rows[0][c['pos']]
+        tiles = sorted(set((c['pos'] // tile).tolist()))
+        twice = int((np.bincount(c['pos']) == 2).sum())
+        print(f'seed {seed}, {name}: candidates per image {[len(x["labels"]) for x in c64]}, in row tiles {tiles}, on levels '
+              f'{np.bincount(lvl[loc], minlength=5).tolist()}, locations with two classes: {twice}')
+        assert len(c64[1]['labels']) == 0 and len(c['labels']) > min(R.EDGE_CAPS) and len(c['labels']) <= max(R.EDGE_CAPS)
+        assert (np.bincount(lvl[loc], minlength=5) > 0).all() and twice >= 1
+        assert set(R.EDGE_ROWS) <= set(loc.tolist())
+        if rows is None:
+            assert min(tiles) < threads and max(tiles) >= threads + 1 and tiles[-1] == 316
+        # no class score is within fp32 reach of the threshold
+        s = R.sigmoid(R.flatten_levels(inp['cls'])[0], np.float64)
+        assert np.abs(s - 0.05).min() > 1e-3
+        assert R.iou_margin(c['boxes'], c['labels'], EDGE_CFG['iou_threshold']) > 1e-4
+    scores = np.sort(c64[0]['scores'])
+    assert np.diff(scores).min() > 1e-4                                                # a shuffled linspace: the order is not fp32's to decide
+    for nms_pre in (1000, -1):
+        out = R.get_bboxes(inp, R.EDGE_STRIDES, R.edge_img_dims(), dict(EDGE_CFG, nms_pre=nms_pre), False, np.float64)
+        print(f'nms_pre {nms_pre}: detections per image {[len(o["labels"]) for o in out]}')
+        assert 0 < len(out[0]['labels']) < len(c64[0]['labels']) and len(out[1]['labels']) == 0
+
+
 def test_greedy_nms_by_hand():
     # A suppresses B, B would suppress C, A does not suppress C: C is kept
     boxes = np.array([[0, 0, 10, 10], [4, 0, 14, 10], [8, 0, 18, 10]], np.float32)
