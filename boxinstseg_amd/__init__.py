@@ -56,6 +56,10 @@ Public surface (mirrors the reference's for this path):
     rle_decode                         <-> pycocotools.mask.decode on the host in numpy (for users and tests)
     solo_encode_results                <-> format_results + encode_mask_results for the SOLOv2-style heads: RLE dicts instead of masks cross to the host
     box2mask_encode_results            <-> MaskFormer.simple_test's formatting + encode_mask_results for Box2Mask, the same way
+    box2mask_loss                      <-> Box2MaskHead.loss: the loss dict of all decoder layers in one call, no sync (csrc/box2mask_loss.hip)
+    Box2MaskLossContext                : what loss_single recomputes per layer (resizes, both trees, edge weights, LCM affinity, box targets), once
+    box2mask_mask_losses               <-> loss_project / loss_levelset of loss_single (:260-335) for the matched rows of all layers together
+    parse_box2mask_head_cfg            : the panoptic_head block of configs/box2mask as box2mask_loss takes it
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -79,6 +83,7 @@ from .box_solo_masks import box_solov2_get_seg_single_kernels, box_solov2_ins_pr
 from .masked_attn import MultiheadAttention, PackedAttnMask, attn_mask_bits, box2mask_attn_mask, masked_attention, pack_attn_mask
 from .inst_post import MaskFormerFusionHead, box2mask_format_results, box2mask_instances, instance_topk
 from .mask_rle import EncodedMasks, box2mask_encode_results, rle_decode, rle_encode, solo_encode_results
+from .box2mask_loss import Box2MaskLossContext, box2mask_loss, box2mask_mask_losses, parse_box2mask_head_cfg
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -100,5 +105,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'box_solov2_ins_preds', 'box_solov2_set_cells', 'box_solov2_get_seg_single_kernels',
            'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention',
            'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results',
-           'rle_encode', 'rle_decode', 'EncodedMasks', 'solo_encode_results', 'box2mask_encode_results']
+           'rle_encode', 'rle_decode', 'EncodedMasks', 'solo_encode_results', 'box2mask_encode_results',
+           'box2mask_loss', 'Box2MaskLossContext', 'box2mask_mask_losses', 'parse_box2mask_head_cfg']
 __version__ = '0.1.0'

@@ -387,6 +387,27 @@ RESULT_FAMILIES = [
     ('rle', ('include/boxinst/boxinst_hip_rle.h',), RLE_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_b2m.h (Box2MaskHead.loss for the matched rows of all decoder layers: scores and their small-grid resize,
+# the level-set energy inside the box without its operands, the LCM refinement with one affinity per image)
+B2M_MAX_LAYERS, B2M_MAX_UP, B2M_MAX_C = 16, 8, 4
+B2M_SIGNATURES = {
+    'bxi_b2m_scores_f32': (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'bxi_b2m_scores_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'bxi_b2m_levelset_state_bytes': (c_size_t, [c_int, c_int]),
+    'bxi_b2m_levelset_forward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                             c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    'bxi_b2m_levelset_backward_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'bxi_b2m_lcm_refine_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]),
+}
+
+# the training steps that are whole compositions: a sixth list, because tests/test_abi_family_rle.py pins RESULT_FAMILIES to ['rle']; the
+# same triples, applied by load() behind the other five with the same check across all lists (tests/test_abi_family_b2m.py)
+TRAIN_FAMILIES = [
+    ('b2m', ('include/boxinst/boxinst_hip_b2m.h',), B2M_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -408,7 +429,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES + TRAIN_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -12,6 +12,7 @@
 //   refined by ONE workgroup in ONE launch, ping-ponging between two LDS planes; the backward is the adjoint operator,
 //   written as a gather (every (p,k) that lands on q after clamping is enumerated) so that it needs no atomics.
 #include "common.hpp"
+#include "lcm_device.hpp"
 
 namespace bxi {
 
@@ -282,6 +283,14 @@ __global__ __launch_bounds__(256) void lcm_affinity_kernel(const float* __restri
     for (int k = 0; k < 8; ++k) aff[((int64_t)n * 8 + k) * hw + p] = e[k] / s;
 }
 
+// The affinity block an instance reads: its own (img_of == nullptr, bxi_lcm_refine_f32) or the one img_of names (bxi_b2m_lcm_refine_f32: one
+// affinity per image, shared by that image's rows); -1 for an index outside [0, n_aff): an inert row, written as zeros.
+__device__ __forceinline__ int lcm_image(const int* __restrict__ img_of, int n_aff, int n) {
+    if (!img_of) return n;
+    const int a = img_of[n];
+    return a >= 0 && a < n_aff ? a : -1;
+}
+
 // one application of the operator (or of its adjoint) at pixel (r,c); src: a plane of h*w floats (LDS or global)
 __device__ __forceinline__ float lcm_apply(const float* __restrict__ A /*[8,h,w] of the instance*/, const float* src, int h, int w,
                                            int d, int r, int c) {
@@ -322,12 +331,14 @@ __device__ __forceinline__ float lcm_apply_adjoint(const float* __restrict__ A, 
 // whole map in LDS: all iterations in one launch, one workgroup per instance
 template <bool ADJ>
 __global__ __launch_bounds__(1024) void lcm_refine_lds_kernel(const float* __restrict__ aff, const float* __restrict__ phi, int h, int w,
-                                                              int d, int iters, float* __restrict__ out) {
+                                                              int d, int iters, float* __restrict__ out, const int* __restrict__ img_of, int n_aff) {
     extern __shared__ __attribute__((aligned(16))) float lcm_planes[];   // [2][h*w]
     const int n = blockIdx.x, tid = threadIdx.x, hw = h * w;
     float* cur = lcm_planes;
     float* nxt = lcm_planes + hw;
-    const float* A = aff + (int64_t)n * 8 * hw;
+    const int ai = lcm_image(img_of, n_aff, n);
+    if (ai < 0) { for (int p = tid; p < hw; p += 1024) out[(int64_t)n * hw + p] = 0.f; return; }
+    const float* A = aff + (int64_t)ai * 8 * hw;
     for (int p = tid; p < hw; p += 1024) cur[p] = phi[(int64_t)n * hw + p];
     __syncthreads();
     for (int it = 0; it < iters; ++it) {
@@ -347,12 +358,14 @@ __global__ __launch_bounds__(1024) void lcm_refine_lds_kernel(const float* __res
 // (b) folding the padding back, g'[q] = sum of gp over the padded positions that replicate q.  Both steps are
 // branch-light, read only LDS (plus the 8 coefficient loads, issued together) and have a fixed summation order.
 __global__ __launch_bounds__(1024) void lcm_adjoint_lds_kernel(const float* __restrict__ aff, const float* __restrict__ gout, int h, int w,
-                                                               int d, int iters, float* __restrict__ gphi) {
+                                                               int d, int iters, float* __restrict__ gphi, const int* __restrict__ img_of, int n_aff) {
     extern __shared__ __attribute__((aligned(16))) float lcm_planes[];   // g [h*w] | gp [(h+2d)*(w+2d)]
     const int n = blockIdx.x, tid = threadIdx.x, hw = h * w, hp = h + 2 * d, wp = w + 2 * d;
     float* g = lcm_planes;
     float* gp = lcm_planes + hw;
-    const float* A = aff + (int64_t)n * 8 * hw;
+    const int ai = lcm_image(img_of, n_aff, n);
+    if (ai < 0) { for (int p = tid; p < hw; p += 1024) gphi[(int64_t)n * hw + p] = 0.f; return; }
+    const float* A = aff + (int64_t)ai * 8 * hw;
     for (int p = tid; p < hw; p += 1024) g[p] = gout[(int64_t)n * hw + p];
     __syncthreads();
     for (int it = 0; it < iters; ++it) {
@@ -402,13 +415,16 @@ __device__ __forceinline__ void lcm_replicas(int r, int c, int h, int w, int d, 
 // 8.5 % more work at 96 x 96, d = 2), so the iterations carry no border case and one barrier each.
 template <int H, int W, int D>
 __global__ __launch_bounds__(kLcmPadThreads) void lcm_refine_pad_kernel(const float* __restrict__ aff, const float* __restrict__ phi,
-                                                                        int h_, int w_, int d_, int iters, float* __restrict__ out) {
+                                                                        int h_, int w_, int d_, int iters, float* __restrict__ out, const int* __restrict__ img_of,
+                                                                        int n_aff) {
     extern __shared__ __attribute__((aligned(16))) float lcm_planes[];   // [2][(h + 2d) * (w + 2d)]
     const int h = H ? H : h_, w = W ? W : w_, d = D ? D : d_;
     const int n = blockIdx.x, tid = threadIdx.x, hw = h * w, hp = h + 2 * d, wp = w + 2 * d, hpwp = hp * wp;
     float* cur = lcm_planes;
     float* nxt = lcm_planes + hpwp;
-    const float* A = aff + (int64_t)n * 8 * hw;
+    const int ai = lcm_image(img_of, n_aff, n);
+    if (ai < 0) { for (int p = tid; p < hw; p += kLcmPadThreads) out[(int64_t)n * hw + p] = 0.f; return; }
+    const float* A = aff + (int64_t)ai * 8 * hw;
     float coef[kLcmPadSPT][8];
     int base[kLcmPadSPT];           // padded index of the top-left tap of the pixel this position replicates; -1: no position
 #pragma unroll
@@ -449,13 +465,16 @@ __global__ __launch_bounds__(kLcmPadThreads) void lcm_refine_pad_kernel(const fl
 // (2d on every side), so (a) is again `plane[base + constant]` without a branch.  Summation orders = lcm_adjoint_lds_kernel's.
 template <int H, int W, int D>
 __global__ __launch_bounds__(kLcmPadThreads) void lcm_adjoint_pad_kernel(const float* __restrict__ aff, const float* __restrict__ gout,
-                                                                         int h_, int w_, int d_, int iters, float* __restrict__ gphi) {
+                                                                         int h_, int w_, int d_, int iters, float* __restrict__ gphi, const int* __restrict__ img_of,
+                                                                         int n_aff) {
     extern __shared__ __attribute__((aligned(16))) float lcm_planes[];   // gz [(h + 4d) * (w + 4d)] | gp [(h + 2d) * (w + 2d)]
     const int h = H ? H : h_, w = W ? W : w_, d = D ? D : d_;
     const int n = blockIdx.x, tid = threadIdx.x, hw = h * w, hp = h + 2 * d, wp = w + 2 * d, wq = w + 4 * d, nq = (h + 4 * d) * wq;
     float* gz = lcm_planes;
     float* gp = lcm_planes + nq;
-    const float* A = aff + (int64_t)n * 8 * hw;
+    const int ai = lcm_image(img_of, n_aff, n);
+    if (ai < 0) { for (int p = tid; p < hw; p += kLcmPadThreads) gphi[(int64_t)n * hw + p] = 0.f; return; }
+    const float* A = aff + (int64_t)ai * 8 * hw;
     for (int i = tid; i < nq; i += kLcmPadThreads) gz[i] = 0.f;
     // The transposed coefficients live in registers for the reference's shape (96 x 96, d = 2: everything about an index is a compile-time
     // constant).  The run-time-shape variant would need 80 registers for them next to run-time strides: it re-reads them (L2-resident,
@@ -582,12 +601,14 @@ __global__ __launch_bounds__(kLcmPadThreads) void lcm_adjoint_pad_kernel(const f
 // any size: one launch per iteration, planes in global memory
 template <bool ADJ>
 __global__ __launch_bounds__(256) void lcm_refine_step_kernel(const float* __restrict__ aff, const float* __restrict__ src, int N, int h,
-                                                              int w, int d, float* __restrict__ dst) {
+                                                              int w, int d, float* __restrict__ dst, const int* __restrict__ img_of, int n_aff) {
     const int64_t hw = (int64_t)h * w;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)N * hw) return;
     const int n = (int)(i / hw), p = (int)(i % hw), r = p / w, c = p % w;
-    const float* A = aff + (int64_t)n * 8 * hw;
+    const int ai = lcm_image(img_of, n_aff, n);
+    if (ai < 0) { dst[i] = 0.f; return; }
+    const float* A = aff + (int64_t)ai * 8 * hw;
     const float* s = src + (int64_t)n * hw;
     dst[i] = ADJ ? lcm_apply_adjoint(A, s, h, w, d, r, c) : lcm_apply(A, s, h, w, d, r, c);
 }
@@ -671,12 +692,22 @@ int bxi_lcm_refine_f32(const float* aff, const float* phi, int N, int h, int w, 
     if (N == 0) return BXI_OK;
     if (!aff || !phi || !out) return BXI_ERR_NULL_POINTER;
     if (!bxi::fits_i32((int64_t)N * h * w * 8)) return BXI_ERR_BAD_SHAPE;
-    hipStream_t s = bxi::as_stream(stream);
+    return bxi::lcm_refine_launch(aff, phi, nullptr, N, N, h, w, dilation, iters, transpose, out, workspace, workspace_bytes, bxi::as_stream(stream));
+}
+
+}  // extern "C"
+
+namespace bxi {
+
+// bxi_lcm_refine_f32 (img_of == nullptr: instance n reads affinity n) and bxi_b2m_lcm_refine_f32 (box2mask_loss.hip: instance n reads
+// affinity img_of[n] of n_aff) behind their argument checks: the same dispatch and the same kernels (lcm_device.hpp)
+int lcm_refine_launch(const float* aff, const float* phi, const int* img_of, int n_aff, int N, int h, int w, int dilation, int iters,
+                      int transpose, float* out, void* workspace, size_t workspace_bytes, hipStream_t s) {
     const size_t lds = sizeof(float) * 2 * (size_t)h * w;
     auto allow_lds = [&](const void* fn, size_t bytes) -> int {
         if (bytes <= 64 * 1024) return BXI_OK;
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) { bxi::set_last_hip_error((int)e); return BXI_ERR_LAUNCH; }
+        if (e != hipSuccess) { set_last_hip_error((int)e); return BXI_ERR_LAUNCH; }
         return BXI_OK;
     };
     const int64_t hp = h + 2 * (int64_t)dilation, wpad = w + 2 * (int64_t)dilation;
@@ -684,51 +715,51 @@ int bxi_lcm_refine_f32(const float* aff, const float* phi, int N, int h, int w, 
     const size_t lds_adj2 = sizeof(float) * (size_t)((h + 4 * (int64_t)dilation) * (w + 4 * (int64_t)dilation) + hp * wpad);
     const bool ref_shape = h == 96 && w == 96 && dilation == 2;           // Box2Mask's LCM (levelset_loss.py:64-66, 96 x 96 targets)
     if (!transpose) {
-        if (hp * wpad <= bxi::kLcmPadSPT * bxi::kLcmPadThreads && lds_fwd <= 128 * 1024) {
-            const void* fn = ref_shape ? reinterpret_cast<const void*>(bxi::lcm_refine_pad_kernel<96, 96, 2>)
-                                       : reinterpret_cast<const void*>(bxi::lcm_refine_pad_kernel<0, 0, 0>);
+        if (hp * wpad <= kLcmPadSPT * kLcmPadThreads && lds_fwd <= 128 * 1024) {
+            const void* fn = ref_shape ? reinterpret_cast<const void*>(lcm_refine_pad_kernel<96, 96, 2>)
+                                       : reinterpret_cast<const void*>(lcm_refine_pad_kernel<0, 0, 0>);
             const int rc = allow_lds(fn, lds_fwd);
             if (rc != BXI_OK) return rc;
             if (ref_shape)
-                BXI_LAUNCH("lcm_refine", s, (bxi::lcm_refine_pad_kernel<96, 96, 2>), dim3(N), dim3(bxi::kLcmPadThreads), lds_fwd, s, aff, phi, h, w, dilation, iters, out);
+                BXI_LAUNCH("lcm_refine", s, (lcm_refine_pad_kernel<96, 96, 2>), dim3(N), dim3(kLcmPadThreads), lds_fwd, s, aff, phi, h, w, dilation, iters, out, img_of, n_aff);
             else
-                BXI_LAUNCH("lcm_refine", s, (bxi::lcm_refine_pad_kernel<0, 0, 0>), dim3(N), dim3(bxi::kLcmPadThreads), lds_fwd, s, aff, phi, h, w, dilation, iters, out);
-            return bxi::check_launch();
+                BXI_LAUNCH("lcm_refine", s, (lcm_refine_pad_kernel<0, 0, 0>), dim3(N), dim3(kLcmPadThreads), lds_fwd, s, aff, phi, h, w, dilation, iters, out, img_of, n_aff);
+            return check_launch();
         }
         if (lds <= 128 * 1024) {
-            const int rc = allow_lds(reinterpret_cast<const void*>(bxi::lcm_refine_lds_kernel<false>), lds);
+            const int rc = allow_lds(reinterpret_cast<const void*>(lcm_refine_lds_kernel<false>), lds);
             if (rc != BXI_OK) return rc;
-            BXI_LAUNCH("lcm_refine", s, bxi::lcm_refine_lds_kernel<false>, dim3(N), dim3(1024), lds, s, aff, phi, h, w, dilation, iters, out);
-            return bxi::check_launch();
+            BXI_LAUNCH("lcm_refine", s, lcm_refine_lds_kernel<false>, dim3(N), dim3(1024), lds, s, aff, phi, h, w, dilation, iters, out, img_of, n_aff);
+            return check_launch();
         }
     } else {
         const size_t lds_adj = sizeof(float) * ((size_t)h * w + (size_t)(h + 2 * dilation) * (w + 2 * dilation));
-        if (hp * wpad <= bxi::kLcmPadSPT * bxi::kLcmPadThreads && (int64_t)h * w <= (bxi::kLcmPadSPT - 1) * bxi::kLcmPadThreads &&
-            2 * (int64_t)w + 2 * (h > 2 ? h - 2 : 0) <= bxi::kLcmPadThreads && lds_adj2 <= 128 * 1024) {
-            const void* fn = ref_shape ? reinterpret_cast<const void*>(bxi::lcm_adjoint_pad_kernel<96, 96, 2>)
-                                       : reinterpret_cast<const void*>(bxi::lcm_adjoint_pad_kernel<0, 0, 0>);
+        if (hp * wpad <= kLcmPadSPT * kLcmPadThreads && (int64_t)h * w <= (kLcmPadSPT - 1) * kLcmPadThreads &&
+            2 * (int64_t)w + 2 * (h > 2 ? h - 2 : 0) <= kLcmPadThreads && lds_adj2 <= 128 * 1024) {
+            const void* fn = ref_shape ? reinterpret_cast<const void*>(lcm_adjoint_pad_kernel<96, 96, 2>)
+                                       : reinterpret_cast<const void*>(lcm_adjoint_pad_kernel<0, 0, 0>);
             const int rc = allow_lds(fn, lds_adj2);
             if (rc != BXI_OK) return rc;
             if (ref_shape)
-                BXI_LAUNCH("lcm_adjoint", s, (bxi::lcm_adjoint_pad_kernel<96, 96, 2>), dim3(N), dim3(bxi::kLcmPadThreads), lds_adj2, s, aff, phi, h, w, dilation, iters, out);
+                BXI_LAUNCH("lcm_adjoint", s, (lcm_adjoint_pad_kernel<96, 96, 2>), dim3(N), dim3(kLcmPadThreads), lds_adj2, s, aff, phi, h, w, dilation, iters, out, img_of, n_aff);
             else
-                BXI_LAUNCH("lcm_adjoint", s, (bxi::lcm_adjoint_pad_kernel<0, 0, 0>), dim3(N), dim3(bxi::kLcmPadThreads), lds_adj2, s, aff, phi, h, w, dilation, iters, out);
-            return bxi::check_launch();
+                BXI_LAUNCH("lcm_adjoint", s, (lcm_adjoint_pad_kernel<0, 0, 0>), dim3(N), dim3(kLcmPadThreads), lds_adj2, s, aff, phi, h, w, dilation, iters, out, img_of, n_aff);
+            return check_launch();
         }
         if (lds_adj <= 128 * 1024) {
-            const int rc = allow_lds(reinterpret_cast<const void*>(bxi::lcm_adjoint_lds_kernel), lds_adj);
+            const int rc = allow_lds(reinterpret_cast<const void*>(lcm_adjoint_lds_kernel), lds_adj);
             if (rc != BXI_OK) return rc;
-            BXI_LAUNCH("lcm_adjoint", s, bxi::lcm_adjoint_lds_kernel, dim3(N), dim3(1024), lds_adj, s, aff, phi, h, w, dilation, iters, out);
-            return bxi::check_launch();
+            BXI_LAUNCH("lcm_adjoint", s, lcm_adjoint_lds_kernel, dim3(N), dim3(1024), lds_adj, s, aff, phi, h, w, dilation, iters, out, img_of, n_aff);
+            return check_launch();
         }
     }
     // large maps: ping-pong between `out` and the workspace plane, one launch per iteration
-    if (!bxi::workspace_ok(workspace, workspace_bytes, bxi_lcm_workspace_bytes(N, h, w), 16))
+    if (!workspace_ok(workspace, workspace_bytes, bxi_lcm_workspace_bytes(N, h, w), 16))
         return BXI_ERR_WORKSPACE;
     const int64_t total = (int64_t)N * h * w;
     if (iters == 0) {
         hipError_t e = hipMemcpyAsync(out, phi, sizeof(float) * total, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) { bxi::set_last_hip_error((int)e); return BXI_ERR_LAUNCH; }
+        if (e != hipSuccess) { set_last_hip_error((int)e); return BXI_ERR_LAUNCH; }
         return BXI_OK;
     }
     float* ws = reinterpret_cast<float*>(workspace);
@@ -736,13 +767,13 @@ int bxi_lcm_refine_f32(const float* aff, const float* phi, int N, int h, int w, 
     const float* src = phi;
     for (int it = 0; it < iters; ++it) {
         float* dst = ((iters - 1 - it) % 2 == 0) ? out : ws;       // the last step writes `out`
-        if (transpose) BXI_LAUNCH("lcm_step", s, bxi::lcm_refine_step_kernel<true>, dim3(grid), dim3(256), 0, s, aff, src, N, h, w, dilation, dst);
-        else BXI_LAUNCH("lcm_step", s, bxi::lcm_refine_step_kernel<false>, dim3(grid), dim3(256), 0, s, aff, src, N, h, w, dilation, dst);
-        const int rc = bxi::check_launch();
+        if (transpose) BXI_LAUNCH("lcm_step", s, lcm_refine_step_kernel<true>, dim3(grid), dim3(256), 0, s, aff, src, N, h, w, dilation, dst, img_of, n_aff);
+        else BXI_LAUNCH("lcm_step", s, lcm_refine_step_kernel<false>, dim3(grid), dim3(256), 0, s, aff, src, N, h, w, dilation, dst, img_of, n_aff);
+        const int rc = check_launch();
         if (rc != BXI_OK) return rc;
         src = dst;
     }
     return BXI_OK;
 }
 
-}  // extern "C"
+}  // namespace bxi
