@@ -130,7 +130,10 @@ def class_maps(T, m0, m1):
 
 def corr_objects(inp, cfg, out_hw, record=False):
     """The loop of :1056-1127 over the N objects of ``inp`` (see INPUT_KEYS); the bank tensors of ``inp`` are updated in place.
-    Returns a dict: loss_sum (differentiable w.r.t. inp['s_feat']), num_ins, iiu [N,2,H,W], and with ``record`` the per-object lists."""
+    Returns a dict: loss_sum (differentiable w.r.t. inp['s_feat']), num_ins, iiu [N,2,H,W], and with ``record`` the per-object lists;
+    among them ``scores`` [N,L,4] (fg, bg, appearance, ratio against the bank as it stood for that object) and ``ret_src`` [N,K], the
+    earlier object of the call whose append put the retrieved entry there, else -1.  An object whose label is outside [0, num_class)
+    is passed over, as the header says: it retrieves nothing (scores 0) and is not appended."""
     s_feat, s_mask, t_feat, t_mask, boxes, labels = (inp[k] for k in INPUT_KEYS[:6])
     bf, bm, bb, ptr = (inp[k] for k in INPUT_KEYS[6:])
     N, L, K = s_feat.shape[0], bf.shape[1], cfg['max_retrieval_objs']
@@ -139,15 +142,22 @@ def corr_objects(inp, cfg, out_hw, record=False):
     loss_sum = torch.zeros(()).to(s_mask)
     num_ins = 0
     rec = dict(ret_slot=-torch.ones(N, K, dtype=torch.int64), count=torch.zeros(N, dtype=torch.int64), Cu=torch.zeros(N, K, 49, 49).to(s_mask),
-               C=torch.zeros(N, K, 49, 49).to(s_mask), assign=-torch.ones(N, K, 49, dtype=torch.int64)) if record else {}
+               C=torch.zeros(N, K, 49, 49).to(s_mask), assign=-torch.ones(N, K, 49, dtype=torch.int64), scores=torch.zeros(N, L, 4).to(s_mask),
+               ret_src=-torch.ones(N, K, dtype=torch.int64)) if record else {}
+    writer = -torch.ones(bf.shape[0], L, dtype=torch.int64)          # who wrote this slot: an object of this call, or -1 (it was stored)
     for i in range(N):
         c = int(labels[i])
+        if not 0 <= c < bf.shape[0]:
+            continue
         with torch.no_grad():
-            keep = torch.where(passing(slot_scores(s_mask[i], s_feat[i].detach(), boxes[i], bm[c], bf[c], bb[c]), cfg))[0][:K]
+            scores = slot_scores(s_mask[i], s_feat[i].detach(), boxes[i], bm[c], bf[c], bb[c])
+            keep = torch.where(passing(scores, cfg))[0][:K]
         n = int(keep.numel())
         if record:
             rec['count'][i] = n
             rec['ret_slot'][i, :n] = keep.cpu()
+            rec['scores'][i] = torch.stack(scores, 1)
+            rec['ret_src'][i, :n] = writer[c][keep.cpu()]
         if n >= cfg['min_objs']:
             f1, m1 = bf[c][keep], bm[c][keep]
             Cu, Cm = solve(s_feat[i], f1, cfg)
@@ -170,6 +180,7 @@ def corr_objects(inp, cfg, out_hw, record=False):
                 s = int(ptr[c])
                 bf[c, s], bm[c, s], bb[c, s] = t_feat[i], t_mask[i], boxes[i]
                 ptr[c] = (s + 1) % L
+                writer[c, s] = i
     out = dict(loss_sum=loss_sum, num_ins=num_ins, iiu=iiu)
     if record:
         out.update(rec)
