@@ -60,6 +60,10 @@ Public surface (mirrors the reference's for this path):
     Box2MaskLossContext                : what loss_single recomputes per layer (resizes, both trees, edge weights, LCM affinity, box targets), once
     box2mask_mask_losses               <-> loss_project / loss_levelset of loss_single (:260-335) for the matched rows of all layers together
     parse_box2mask_head_cfg            : the panoptic_head block of configs/box2mask as box2mask_loss takes it
+    discobox_loss                      <-> DiscoBoxSOLOv2Head.loss: the loss dict in one call, the only sync is solov2_targets' (csrc/discobox_loss.hip)
+    discobox_pseudo_losses             <-> the mil / ts / ts_corr terms of loss (:1271-1306) and corr_loss (:1127-1137) for the rows of all levels: labels as bits
+    live_means                         : the means over the rows whose target is not all zero, decided on the device
+    parse_discobox_loss_cfg            : loss_ins / loss_ts / loss_corr of the bbox_head block of configs/discobox as discobox_loss reads them
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -84,6 +88,7 @@ from .masked_attn import MultiheadAttention, PackedAttnMask, attn_mask_bits, box
 from .inst_post import MaskFormerFusionHead, box2mask_format_results, box2mask_instances, instance_topk
 from .mask_rle import EncodedMasks, box2mask_encode_results, rle_decode, rle_encode, solo_encode_results
 from .box2mask_loss import Box2MaskLossContext, box2mask_loss, box2mask_mask_losses, parse_box2mask_head_cfg
+from .discobox_loss import discobox_loss, discobox_pseudo_losses, live_means, parse_discobox_loss_cfg
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -106,5 +111,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'PackedAttnMask', 'attn_mask_bits', 'box2mask_attn_mask', 'pack_attn_mask', 'masked_attention', 'MultiheadAttention',
            'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results',
            'rle_encode', 'rle_decode', 'EncodedMasks', 'solo_encode_results', 'box2mask_encode_results',
-           'box2mask_loss', 'Box2MaskLossContext', 'box2mask_mask_losses', 'parse_box2mask_head_cfg']
+           'box2mask_loss', 'Box2MaskLossContext', 'box2mask_mask_losses', 'parse_box2mask_head_cfg',
+           'discobox_loss', 'discobox_pseudo_losses', 'live_means', 'parse_discobox_loss_cfg']
 __version__ = '0.1.0'

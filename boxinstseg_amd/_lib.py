@@ -408,6 +408,28 @@ TRAIN_FAMILIES = [
     ('b2m', ('include/boxinst/boxinst_hip_b2m.h',), B2M_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_dbx.h (the pseudo-label block of DiscoBoxSOLOv2Head.loss for the rows of all levels: labels as bit words, both
+# mean-field legs in one launch per iteration, the dice terms from the words, the means over the live rows)
+DBX_MAX_LEVELS, DBX_MAX_MEANS, DBX_TARGET, DBX_ENLARGED, DBX_LABEL = 8, 4, 0, 1, 2
+DBX_SIGNATURES = {
+    'bxi_dbx_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'bxi_dbx_prepare_f32': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_dbx_steps_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, C.c_double, c_int, C.POINTER(c_void_p),
+                                  C.POINTER(c_int), c_int, c_void_p, c_size_t, c_void_p]),
+    'bxi_dbx_dice_forward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    'bxi_dbx_dice_backward_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, C.c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    'bxi_dbx_means_f32': (c_int, [C.POINTER(c_void_p), c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'bxi_dbx_means_backward_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    'bxi_dbx_unpack_u8': (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+}
+
+# the training steps of the second SOLOv2-style method: a seventh list, because tests/test_abi_family_b2m.py pins TRAIN_FAMILIES to
+# ['b2m']; the same triples, applied by load() behind the other six with the same check across all lists (tests/test_abi_family_dbx.py)
+PSEUDO_FAMILIES = [
+    ('dbx', ('include/boxinst/boxinst_hip_dbx.h',), DBX_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -429,7 +451,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES + TRAIN_FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES + TRAIN_FAMILIES + PSEUDO_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

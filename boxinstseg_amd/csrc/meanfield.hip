@@ -17,6 +17,7 @@
 // dice_loss / mil_loss: row-wise reductions + dense, atomic-free backward (same structure as the BoxInst
 // projection term, but on probabilities, arbitrary 0/1 targets and the +0.001 form of the dice).
 #include "common.hpp"
+#include "meanfield_device.hpp"   // MfArgs, mf_first_item, mf_eval_item: the step discobox_loss.hip shares
 
 namespace bxi {
 
@@ -59,35 +60,8 @@ __global__ __launch_bounds__(256) void mf_kernel_build(const float* __restrict__
 // ~130 VALU instructions per pixel and iteration then sit on ONE CU per instance -- 390 us for 16 instances while
 // 240 CUs idle; a launch boundary costs 2.5 us).  Items whose target word is empty exit at once: outside the target
 // the state is constantly low (f[:, 1:] *= targets, :649).
-typedef unsigned long long u64;
-
-struct MfArgs {
-    const float* K;           // [B,KS*KS,H,W]
-    const float* x;           // [N,H,W]
-    const void* t;            // [N,H,W] f32 or u8
-    const int64_t* img;       // [N] or null
-    const float* inter;       // [N,2,H,W] or null
-    float* ret;               // [N,H,W]
-    float* valid;             // [N]
-    u64* tw;                  // [N,H,segs] target words
-    u64* sa;                  // [N,H,segs] state, read
-    u64* sb;                  // [N,H,segs] state, written
-    int B, H, W, N, t_u8, segs;
-    float nl_lo0, nl_lo1, nl_hi0, nl_hi1;   // -log(1-x), -log(x) for x = lo / hi
-    float gamma, vlo, vhi;
-};
-
-constexpr int kMfWaves = 4;   // waves per workgroup of the per-item kernels
 constexpr int kMfManyItems = 32768;   // more (instance, row, segment) items than this: 4 items per wave (_lib.MF_MANY_ITEMS)
-// IPW = consecutive items per wave: 4 when there are many items (4x fewer workgroups to dispatch), 1 when few
-// (all the parallelism there is)
-
-// first item of this wave
-template <int IPW>
-__device__ __forceinline__ int mf_first_item() {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    return ((int)blockIdx.x * kMfWaves + wave) * IPW;
-}
+bool mf_many_items(int64_t items) { return items > kMfManyItems; }      // meanfield_device.hpp: discobox_loss.hip makes the same choice
 
 // initial state (:621-622) and the target mask
 template <int IPW>
@@ -118,61 +92,6 @@ __global__ __launch_bounds__(256) void mf_init_kernel(MfArgs a) {
             a.tw[w] = mt; a.sa[w] = ms; a.sb[w] = 0ull;      // both buffers: items without target are never written again
         }
     }
-}
-
-// one simple_forward (:640-655) of every item
-template <int KS>
-__device__ __forceinline__ void mf_eval_item(const MfArgs& a, const u64* sa, u64* sb, int n, int r, int sg, u64 mt, int lane) {
-    constexpr int HALF = KS / 2, KK = KS * KS;
-    const int H = a.H, W = a.W, segs = a.segs, c = sg * 64 + lane;
-    const int64_t wbase = (int64_t)n * H * segs;
-    const int64_t HW = (int64_t)H * W;
-    const int cc = c < W ? c : W - 1;                             // clamped: loads need no branch
-    // img_inds is device data: clamp it into [0, B) so that a bad index reads a wrong kernel plane, never foreign memory
-    const int64_t bi = a.img ? (a.img[n] < 0 ? 0 : (a.img[n] >= a.B ? a.B - 1 : a.img[n])) : 0;
-    const float* Kp = a.K + bi * (int64_t)KK * HW + (int64_t)r * W + cc;
-    float kv[KK];
-#pragma unroll
-    for (int k = 0; k < KK; ++k) kv[k] = Kp[(int64_t)k * HW];
-    float i0 = 0.f, i1 = 0.f;
-    if (a.inter) { const float* ip = a.inter + (int64_t)n * 2 * HW + (int64_t)r * W + cc; i0 = ip[0]; i1 = ip[HW]; }
-    // the state words of the neighbourhood rows (uniform addresses); outside the map = 0 and never used
-    u64 wl[KS], wm[KS], wr[KS];
-#pragma unroll
-    for (int dy = -HALF; dy <= HALF; ++dy) {
-        const int r2 = r + dy;
-        const bool rin = r2 >= 0 && r2 < H;
-        const u64* row = sa + wbase + (int64_t)(rin ? r2 : r) * segs;
-        wm[dy + HALF] = rin ? row[sg] : 0ull;
-        wl[dy + HALF] = rin && sg > 0 ? row[sg - 1] : 0ull;
-        wr[dy + HALF] = rin && sg + 1 < segs ? row[sg + 1] : 0ull;
-    }
-    const bool act = (mt >> lane) & 1ull;
-    float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-    for (int dy = -HALF; dy <= HALF; ++dy) {
-        const int r2 = r + dy;
-        const bool rin = r2 >= 0 && r2 < H;
-#pragma unroll
-        for (int dx = -HALF; dx <= HALF; ++dx) {
-            const int k = (dy + HALF) * KS + (dx + HALF);
-            const u64 m = wm[dy + HALF];
-            const u64 sh = dx < 0 ? (m << (-dx)) | (wl[dy + HALF] >> (64 + dx)) : dx > 0 ? (m >> dx) | (wr[dy + HALF] << (64 - dx)) : m;
-            const bool bit = (sh >> lane) & 1ull;
-            const int c2 = c + dx;
-            if (rin && c2 >= 0 && c2 < W) {                   // outside the map nn.Unfold pads -log(U) with 0: adds nothing
-                acc0 = __fadd_rn(acc0, __fmul_rn(bit ? a.nl_hi0 : a.nl_lo0, kv[k]));
-                acc1 = __fadd_rn(acc1, __fmul_rn(bit ? a.nl_hi1 : a.nl_lo1, kv[k]));
-            }
-        }
-    }
-    float f0 = expf(-acc0), f1 = expf(-acc1);
-    if (a.inter) { f0 = __fadd_rn(f0, __fmul_rn(i0, a.gamma)); f1 = __fadd_rn(f1, __fmul_rn(i1, a.gamma)); }
-    f1 = act ? f1 : 0.f;                                      // f[:, 1:] *= targets
-    f0 = __fadd_rn(f0, 1e-6f); f1 = __fadd_rn(f1, 1e-6f);
-    const float r1v = __fdiv_rn(f1, __fadd_rn(f0, f1));
-    const u64 nw = __ballot(act && c < W && r1v > 0.5f);
-    if (lane == 0) sb[wbase + (int64_t)r * segs + sg] = nw;
 }
 
 // One launch per iteration.  (Tried: all iterations in one launch of a persistent grid meeting at an agent-scope
@@ -457,11 +376,7 @@ int bxi_meanfield_forward_f32(const float* kernel, int B, int H, int W, int ksiz
     a.B = B; a.H = H; a.W = W; a.N = N; a.t_u8 = targets_u8 ? 1 : 0; a.segs = (W + 63) / 64;
     const size_t plane = (size_t)N * H * a.segs;
     a.tw = reinterpret_cast<bxi::u64*>(workspace); a.sa = a.tw + plane; a.sb = a.sa + plane;
-    // the two values a thresholded probability takes, (f > 0.5).float() * (1 - base*2) + base (:622, :653), in fp32
-    const float span = (float)(1.0 - (double)base * 2.0);
-    const float lo = 0.f * span + base, hi = 1.f * span + base;
-    a.nl_lo0 = -logf(1.f - lo); a.nl_lo1 = -logf(lo);
-    a.nl_hi0 = -logf(1.f - hi); a.nl_hi1 = -logf(hi);
+    bxi::mf_set_levels(a, base);
     a.gamma = gamma;
     a.vlo = (float)((double)(H * W) * 0.05); a.vhi = (float)((double)(H * W) * 0.95);
     hipStream_t s = bxi::as_stream(stream);

@@ -164,6 +164,17 @@ def _run(plan, kernel_preds_raw, ins_pred, compute='fp32', out_dtype=None):
     return _lists(plan, out, img)
 
 
+def _dynamic_rows(kernel_preds_raw, grid_order, ins_pred, sigmoid=True, status=None, cells=None):
+    """The fp32 row buffer itself, for callers inside the package (discobox_loss): ``(rows [N,H,W], img_inds [N], rows per level, cells)``, level-major --
+    what ``solo_dynamic_masks`` slices into its per-level views.  ``cells``: the cell vector of an earlier call with the same ``grid_order``."""
+    kernel_preds_raw = list(kernel_preds_raw)
+    plan = _plan(kernel_preds_raw, grid_order, ins_pred, sigmoid, status)
+    if cells is not None:
+        plan.cells = cells
+    out, img = _DynamicMasks.apply(plan, _fp32(ins_pred), *[_fp32(m) for m in kernel_preds_raw])
+    return out, img, [sum(plan.counts[l * plan.B:(l + 1) * plan.B]) for l in range(plan.L)], plan.cells
+
+
 def _check_compute(compute, out_dtype, **tensors):
     """``compute`` is 'fp32' or 'half'; with 'half' every tensor is of ONE half dtype (checked before anything else, so that it is said
     without a device) and ``out_dtype`` is None, that dtype or torch.float32; with 'fp32' the masks are fp32."""

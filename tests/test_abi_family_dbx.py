@@ -1,0 +1,104 @@
+"""The seventh list of ABI families of boxinstseg_amd/_lib.py (PSEUDO_FAMILIES: the pseudo-label block of DiscoBoxSOLOv2Head.loss, which
+arrived after tests/test_abi_families.py pinned FAMILIES, tests/test_abi_family_inst.py pinned LATE_FAMILIES,
+tests/test_abi_family_dconv16.py pinned HALF_FAMILIES, tests/test_abi_family_dconvl.py pinned LEVEL_FAMILIES,
+tests/test_abi_family_rle.py pinned RESULT_FAMILIES and tests/test_abi_family_b2m.py pinned TRAIN_FAMILIES) against its headers, the
+library's exports and the guarded GPU tests: the four checks of tests/test_abi_family_b2m.py, for this list.
+
+* what the family's header declares = the keys of its signature table = exported symbols, with the tabled restype / argtypes applied and
+  as many parameters as the C declaration has;
+* no name shared with any table or header of any family of any of the seven lists; a duplicate fails at load with the unchanged message;
+* every entry point is run guarded by a named test of tests/test_gpu_guarded_dbx_loss.py (its GUARDED table) or exempt here as a size query.
+No GPU needed: only the built library."""
+import importlib
+import inspect
+
+import pytest
+
+from boxinstseg_amd import _lib
+from tests.test_abi_families import _declarations
+
+GUARDED_MODULES = {'dbx': ('test_gpu_guarded_dbx_loss',)}
+# entry point -> why no guarded test runs it: nothing here launches a kernel over caller memory
+EXEMPT = {'bxi_dbx_workspace_bytes': 'size query'}
+EARLIER = _lib.FAMILIES + _lib.LATE_FAMILIES + _lib.HALF_FAMILIES + _lib.LEVEL_FAMILIES + _lib.RESULT_FAMILIES + _lib.TRAIN_FAMILIES
+EVERY = EARLIER + _lib.PSEUDO_FAMILIES
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _built(built):
+    return built
+
+
+def test_pseudo_families_are_the_dbx_table():
+    assert [name for name, _, _ in _lib.PSEUDO_FAMILIES] == ['dbx'] and _lib.PSEUDO_FAMILIES[0][2] is _lib.DBX_SIGNATURES
+    assert _lib.PSEUDO_FAMILIES[0][1] == ('include/boxinst/boxinst_hip_dbx.h',)
+    assert sorted(_lib.DBX_SIGNATURES) == ['bxi_dbx_dice_backward_f32', 'bxi_dbx_dice_forward_f32', 'bxi_dbx_means_backward_f32', 'bxi_dbx_means_f32',
+                                           'bxi_dbx_prepare_f32', 'bxi_dbx_steps_f32', 'bxi_dbx_unpack_u8', 'bxi_dbx_workspace_bytes']
+    assert set(GUARDED_MODULES) == {name for name, _, _ in _lib.PSEUDO_FAMILIES}
+    assert len({name for name, _, _ in EVERY}) == len(EVERY)
+    assert all(table is not _lib.DBX_SIGNATURES for _, _, table in EARLIER)
+    assert _lib.load().bxi_abi_version() == _lib.BXI_ABI_VERSION == 7          # additive: the version stays
+
+
+@pytest.mark.parametrize('family,headers,table', _lib.PSEUDO_FAMILIES, ids=[f[0] for f in _lib.PSEUDO_FAMILIES])
+def test_header_exports_and_signatures_agree(family, headers, table):
+    lib = _lib.load()
+    decls = _declarations(headers)
+    assert decls, 'no declarations found'
+    for n in decls:
+        assert hasattr(lib, n), f'{n} declared in {headers} but not exported'
+        assert n in table, f'{n} has no ctypes signature in the {family} table'
+    assert sorted(table) == sorted(decls)
+    for n, (res, args) in table.items():
+        fn = getattr(lib, n)
+        assert fn.restype == res and list(fn.argtypes) == list(args), n
+        assert len(decls[n]) == len(args), f'{n}: {len(decls[n])} parameters declared, {len(args)} tabled'
+    for other, other_headers, other_table in EVERY:
+        if other != family:
+            assert not set(table) & set(other_table), (family, other, sorted(set(table) & set(other_table)))
+            again = set(decls) & set(_declarations(other_headers))
+            assert not again, f'{sorted(again)} of {family} declared again in {other_headers}'
+
+
+@pytest.mark.parametrize('family,table', [(f[0], f[2]) for f in _lib.PSEUDO_FAMILIES], ids=[f[0] for f in _lib.PSEUDO_FAMILIES])
+def test_a_name_in_two_families_fails_at_load(monkeypatch, family, table):
+    name = sorted(table)[0]
+    monkeypatch.setattr(_lib, '_lib', None)
+    monkeypatch.setattr(_lib, 'PSEUDO_FAMILIES', _lib.PSEUDO_FAMILIES + [('again', (), {name: table[name]})])
+    with pytest.raises(RuntimeError, match=f'{name} is in the signature tables of two ABI families: {family} and again'):
+        _lib.load()
+    # and across the lists: a name of the first table of each of the six earlier lists, in this one
+    for first_family, _, first_table in (_lib.FAMILIES[0], _lib.LATE_FAMILIES[0], _lib.HALF_FAMILIES[0], _lib.LEVEL_FAMILIES[0], _lib.RESULT_FAMILIES[0],
+                                         _lib.TRAIN_FAMILIES[0]):
+        stolen = sorted(first_table)[0]
+        monkeypatch.setattr(_lib, '_lib', None)
+        monkeypatch.setattr(_lib, 'PSEUDO_FAMILIES', [('pseudo', (), {stolen: first_table[stolen]})])
+        with pytest.raises(RuntimeError, match=f'{stolen} is in the signature tables of two ABI families: {first_family} and pseudo'):
+            _lib.load()
+
+
+def _guarded(family):
+    """entry point -> (module, test) over the family's GUARDED tables: the named test exists and its module makes the call."""
+    found = {}
+    for mod_name in GUARDED_MODULES[family]:
+        mod = importlib.import_module('tests.' + mod_name)
+        for entry, test in mod.GUARDED.items():
+            assert entry not in found, f'{entry} is listed twice'
+            fn = getattr(mod, test, None)
+            assert callable(fn) and test.startswith('test_'), f'{entry}: {mod_name} has no test {test}'
+            assert '_call(' in inspect.getsource(fn), (entry, test)
+            assert 'lib.' + entry + '(' in inspect.getsource(mod._call), entry
+            found[entry] = (mod_name, test)
+    return found
+
+
+@pytest.mark.parametrize('family,table', [(f[0], f[2]) for f in _lib.PSEUDO_FAMILIES], ids=[f[0] for f in _lib.PSEUDO_FAMILIES])
+def test_every_entry_point_is_guarded_or_exempt(family, table):
+    mine = set(_guarded(family))
+    exempt = set(EXEMPT) & set(table)
+    assert not mine & exempt, sorted(mine & exempt)
+    missing = set(table) - mine - exempt
+    assert not missing, f'{family}: neither run by a guarded test (GUARDED) nor exempt with a reason (EXEMPT): {sorted(missing)}'
+    assert mine | exempt == set(table), f'{family}: not in its signature table any more: {sorted((mine | exempt) - set(table))}'
+    for entry, reason in EXEMPT.items():
+        assert reason and '_bytes' in entry, entry
