@@ -64,6 +64,10 @@ Public surface (mirrors the reference's for this path):
     discobox_pseudo_losses             <-> the mil / ts / ts_corr terms of loss (:1271-1306) and corr_loss (:1127-1137) for the rows of all levels: labels as bits
     live_means                         : the means over the rows whose target is not all zero, decided on the device
     parse_discobox_loss_cfg            : loss_ins / loss_ts / loss_corr of the bbox_head block of configs/discobox as discobox_loss reads them
+    box_solov2_loss                    <-> BoxSOLOv2Head.loss: the loss dict in one call, the only sync is box_solov2_targets' (csrc/boxlevelset_loss.hip)
+    BoxLevelSetLossContext             : what the level loop recomputes per level, image and set cell (resizes, both trees, orders, edge weights), once per size
+    box_solov2_mask_losses             <-> loss_boxpro / loss_levelset of loss (:334-367) for the set cells of all levels together, rows of different sizes in one launch
+    parse_box_solov2_loss_cfg          : loss_boxpro / loss_levelset / loss_cate of the bbox_head block of configs/boxlevelset as box_solov2_loss reads them
 """
 from .pairwise import PairwiseNLog, pairwise_nlog, pairwise_nlog_backward, pairwise_nlog_forward
 from .functional import BoxInstMaskLoss, box_bitmasks, boxinst_mask_loss, color_affinity
@@ -89,6 +93,7 @@ from .inst_post import MaskFormerFusionHead, box2mask_format_results, box2mask_i
 from .mask_rle import EncodedMasks, box2mask_encode_results, rle_decode, rle_encode, solo_encode_results
 from .box2mask_loss import Box2MaskLossContext, box2mask_loss, box2mask_mask_losses, parse_box2mask_head_cfg
 from .discobox_loss import discobox_loss, discobox_pseudo_losses, live_means, parse_discobox_loss_cfg
+from .boxlevelset_loss import BoxLevelSetLossContext, box_solov2_loss, box_solov2_mask_losses, parse_box_solov2_loss_cfg
 from .config import load_config
 
 __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', 'PairwiseNLog',
@@ -112,5 +117,6 @@ __all__ = ['pairwise_nlog', 'pairwise_nlog_forward', 'pairwise_nlog_backward', '
            'instance_topk', 'box2mask_instances', 'MaskFormerFusionHead', 'box2mask_format_results',
            'rle_encode', 'rle_decode', 'EncodedMasks', 'solo_encode_results', 'box2mask_encode_results',
            'box2mask_loss', 'Box2MaskLossContext', 'box2mask_mask_losses', 'parse_box2mask_head_cfg',
-           'discobox_loss', 'discobox_pseudo_losses', 'live_means', 'parse_discobox_loss_cfg']
+           'discobox_loss', 'discobox_pseudo_losses', 'live_means', 'parse_discobox_loss_cfg',
+           'box_solov2_loss', 'BoxLevelSetLossContext', 'box_solov2_mask_losses', 'parse_box_solov2_loss_cfg']
 __version__ = '0.1.0'

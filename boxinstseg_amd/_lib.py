@@ -430,6 +430,37 @@ PSEUDO_FAMILIES = [
     ('dbx', ('include/boxinst/boxinst_hip_dbx.h',), DBX_SIGNATURES),
 ]
 
+# include/boxinst/boxinst_hip_bls.h (the mask losses of BoxSOLOv2Head.loss for the set cells of all levels: scores, projection term, pixel_num
+# and image level-set energy in one pass, the level-set energy on the rows' own filter outputs, one backward launch for every level's gradient)
+BLS_MAX_GROUPS, BLS_MAX_LEVELS, BLS_MAX_W, BLS_CHUNK_PIXELS, BLS_LEVEL_ROWS = 4, 8, 2048, 1024, 1 << 20
+
+
+class BlsGroup(C.Structure):
+    """struct bxi_bls_group"""
+    _fields_ = [('img', c_void_p), ('masks', c_void_p), ('h', c_int), ('w', c_int), ('rows', c_int), ('G', c_int)]
+
+
+BLS_SIGNATURES = {
+    'bxi_bls_state_bytes': (c_size_t, [C.POINTER(BlsGroup), c_int]),
+    'bxi_bls_front_f32': (c_int, [C.POINTER(BlsGroup), c_int, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), c_int, c_void_p, c_void_p,
+                                  c_void_p, c_int, c_int, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_size_t, c_void_p]),
+    'bxi_bls_backward_f32': (c_int, [C.POINTER(BlsGroup), c_int, C.POINTER(c_void_p), C.POINTER(c_int), C.POINTER(c_int), c_int, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_int, C.c_double, C.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
+    'bxi_bls_high_state_bytes': (c_size_t, [C.POINTER(BlsGroup), c_int]),
+    'bxi_bls_high_forward_f32': (c_int, [C.POINTER(BlsGroup), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, C.c_double,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    'bxi_bls_high_backward_f32': (c_int, [C.POINTER(BlsGroup), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, C.c_double,
+                                          c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
+# the training steps of the third SOLOv2-style method: an eighth list, because tests/test_abi_family_dbx.py pins PSEUDO_FAMILIES to
+# ['dbx']; the same triples, applied by load() behind the other seven with the same check across all lists (tests/test_abi_family_bls.py)
+LEVELSET_FAMILIES = [
+    ('bls', ('include/boxinst/boxinst_hip_bls.h',), BLS_SIGNATURES),
+]
+
 LAUNCH_HOOK = C.CFUNCTYPE(None, C.c_char_p, c_int, c_void_p, c_void_p)
 
 _lib: Optional[C.CDLL] = None
@@ -451,7 +482,7 @@ def load() -> C.CDLL:
                 'boxinstseg_amd has no CPU or PyTorch fallback for this path.')
         lib = C.CDLL(path)
         owner = {}
-        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES + TRAIN_FAMILIES + PSEUDO_FAMILIES:
+        for family, _, table in FAMILIES + LATE_FAMILIES + HALF_FAMILIES + LEVEL_FAMILIES + RESULT_FAMILIES + TRAIN_FAMILIES + PSEUDO_FAMILIES + LEVELSET_FAMILIES:
             for name, (res, args) in table.items():
                 if owner.setdefault(name, family) != family:
                     raise RuntimeError(f'{name} is in the signature tables of two ABI families: {owner[name]} and {family}')

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB_DIR = os.path.join(HERE, 'lib')
 LIB_PATH = os.path.join(LIB_DIR, 'libboxinst_hip.so')
-SOURCES = ['abi.hip', 'pairwise_op.hip', 'color_affinity.hip', 'mask_loss.hip', 'fused_eval.hip', 'dynamic_head.hip', 'dynamic_head_generic.hip', 'meanfield.hip', 'levelset.hip', 'tree_filter.hip', 'tree_filter_large.hip', 'sol_eval.hip', 'mask_paste.hip', 'matrix_nms.hip', 'box_match.hip', 'box_nms.hip', 'fcos_loss.hip', 'solo_targets.hip', 'corr.hip', 'roi_align.hip', 'msda.hip', 'seg_paste.hip', 'solo_dconv.hip', 'masked_attn.hip', 'inst_post.hip', 'solo_dconv16.hip', 'solo_dconv_level.hip', 'mask_rle.hip', 'box2mask_loss.hip', 'discobox_loss.hip']
+SOURCES = ['abi.hip', 'pairwise_op.hip', 'color_affinity.hip', 'mask_loss.hip', 'fused_eval.hip', 'dynamic_head.hip', 'dynamic_head_generic.hip', 'meanfield.hip', 'levelset.hip', 'tree_filter.hip', 'tree_filter_large.hip', 'sol_eval.hip', 'mask_paste.hip', 'matrix_nms.hip', 'box_match.hip', 'box_nms.hip', 'fcos_loss.hip', 'solo_targets.hip', 'corr.hip', 'roi_align.hip', 'msda.hip', 'seg_paste.hip', 'solo_dconv.hip', 'masked_attn.hip', 'inst_post.hip', 'solo_dconv16.hip', 'solo_dconv_level.hip', 'mask_rle.hip', 'box2mask_loss.hip', 'discobox_loss.hip', 'boxlevelset_loss.hip']
 HEADERS = ['common.hpp', 'lcm_device.hpp', 'meanfield_device.hpp', 'solo_dconv_device.hpp', 'paste_device.hpp', 'image_device.hpp', 'loss_common.hpp', 'focal_device.hpp', 'dynamic_head_device.hpp', 'eval_protocol_device.hpp', 'eval_front_device.hpp',
            'eval_tile_device.hpp', 'eval_back_device.hpp', 'srgb_lut.h', os.path.join('..', '..', 'include', 'boxinst_hip.h'),
            os.path.join('..', '..', 'include', 'boxinst_hip_dev.h'), os.path.join('..', '..', 'include', 'boxinst_hip_plan.h'),
@@ -25,7 +25,8 @@ HEADERS = ['common.hpp', 'lcm_device.hpp', 'meanfield_device.hpp', 'solo_dconv_d
            os.path.join('..', '..', 'include', 'boxinst', 'boxinst_hip_dconvl.h'),
            os.path.join('..', '..', 'include', 'boxinst', 'boxinst_hip_rle.h'),
            os.path.join('..', '..', 'include', 'boxinst', 'boxinst_hip_b2m.h'),
-           os.path.join('..', '..', 'include', 'boxinst', 'boxinst_hip_dbx.h')]
+           os.path.join('..', '..', 'include', 'boxinst', 'boxinst_hip_dbx.h'),
+           os.path.join('..', '..', 'include', 'boxinst', 'boxinst_hip_bls.h')]
 ARCH = 'gfx950'
 
 
