@@ -20,15 +20,18 @@ struct B2mLayers { const float* p[BXI_B2M_MAX_LAYERS]; };
 // One axis of F.interpolate(mode='bilinear', align_corners=False): source index scale * (o + 0.5) - 0.5 clamped at 0, taps i0 and
 // i1 = min(i0 + 1, n - 1), weights 1 - l1 and l1 (UpSample.h: area_pixel_compute_source_index, upsample_bilinear2d).  The index is taken in
 // double: in float its fraction carries an absolute error of an ulp of the INDEX (1.5e-5 at index 200), which torch's own kernels differ by
-// among themselves; the weights here are the correctly rounded ones.
+// among themselves; the weights here are the correctly rounded ones.  BOTH of them: 1.f - l1 carries l1's absolute error of up to 2^-25
+// into a weight that may itself be small (1/24 at 200 -> 96: twelve times the relative error of one rounding, which the adjoint's elements
+// with a single tap show in full), so l0 is rounded from the double as well.
 __device__ __forceinline__ void b2m_axis(int o, double scale, int n_in, int& i0, int& i1, float& l0, float& l1) {
     double src = scale * ((double)o + 0.5) - 0.5;
     if (src < 0.0) src = 0.0;
     i0 = (int)src;
     if (i0 > n_in - 1) i0 = n_in - 1;
     i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    l1 = (float)(src - (double)i0);
-    l0 = 1.f - l1;
+    const double frac = src - (double)i0;
+    l1 = (float)frac;
+    l0 = (float)(1.0 - frac);
 }
 
 __device__ __forceinline__ float b2m_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
